@@ -16,8 +16,16 @@ meet in ONE RCCL all-gather of per-cycle score rows.
   --ffn sparse|dense|both   weight recipe of the decoder FFN.  "sparse" (the headline): devqa_amd.synth style "opt" -- fc1 bias
                     -0.3 and a narrow fc1 so that ~2 % of the ReLU units fire, as in a trained OPT; the FT loop then runs on the
                     active columns only.  "dense": SURVEY.md 8(d)'s recipe verbatim (N(0, 0.02) weights, biases 0): half of
-                    the units fire, no compaction.  "both" (default): the sparse headline plus a short dense leg reported beside it.
+                    the units fire, no compaction.  "both" (default): the sparse headline plus a short dense leg reported beside it (--full).
   --selftest-cpu    no GPU, gloo: walks the launcher / sharding / collective / JSON code with fake cycles (tests/test_dist_cpu.py).
+
+A plain run times the headline leg only: set up, W warm-up steps, K timed steps, the result line.  --full adds everything else the
+line used to carry: the slot profiler's event pairs in the timed region and the figures read from them (`roofline`, `kernels`,
+`roofline_hbm`), the other scaling leg, the dense-FFN leg (--ffn both), the CPU baseline with the full-depth parity block and the
+BASELINE configs #3-#5; their --no-* switches act under --full.
+  --dump-outputs DIR   after the timed steps, rank 0 writes what its last timed step returned (per-cycle probe accuracies, executed FT steps,
+                       per-step FT losses, the decoded post-/pre-edit token ids) as DIR/<name>.npy, float32: the same arguments give the
+                       same inputs, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
@@ -41,6 +49,7 @@ SPARSE_RECIPE = ("synthetic weights, numpy recipe 'opt' (devqa_amd/synth.py): de
 DENSE_RECIPE = "SURVEY 8(d) recipe verbatim: every weight N(0, 0.02), LayerNorm weight 1, all biases 0 (dense ReLU FFN, no column compaction)"
 
 
+IMAGE_TAGS = ("i1", "ir", "i2", "i3")  # the images of one synthetic cycle (devqa_amd.synth.evqa_cycles)
 PROF = {"frac": 1.0, "steps": []}      # share of the last timed region that carried the slot profiler's event pairs (timed_leg)
 
 
@@ -73,6 +82,11 @@ def parse_args(argv=None):
                          "region -- the rate a caller sees who hands over host buffers (DESIGN 7)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--selftest-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: roofline / kernel figures, the other scaling leg, the dense-FFN leg, the CPU "
+                         "baseline + parity, the HBM micro-measurements, configs #3-#5 (off: set up, warm up, time --steps, print the line)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -427,22 +441,39 @@ class Leg:
         scaling = scaling or a.scaling
         proc, size, vocab = self.vllm.image_processor, self.cfg["vision_config"]["image_size"], self.cfg["text_config"]["vocab_size"]
 
+        def put(key, arr):
+            px = torch.from_numpy(arr)
+            self._img_cache[key] = px.pin_memory() if getattr(a, "host_pixels", False) else px.to(self.dev)
+
+        def prefetch(samples):
+            """Pre-processed pixels of every image of these samples, computed on a thread pool (the numpy / PIL work is most of the
+            set-up time of a run; every image is a function of (seed, sample, tag) alone, so the values do not depend on the order)."""
+            keys = [(s, t) for s in samples for t in IMAGE_TAGS if (s, t) not in self._img_cache]
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(build_threads(self.world)) as ex:
+                for i in range(0, len(keys), 256):
+                    chunk = keys[i:i + 256]
+                    for key, arr in zip(chunk, ex.map(lambda k: proc(self._synth_image_u8(k[0], k[1], size, a.seed)), chunk)):
+                        put(key, arr)
+
         def image_of_factory(offset):
             def image_of(s, tag):
                 key = (offset + s, tag)
                 if key not in self._img_cache:
-                    px = torch.from_numpy(proc(self._synth_image_u8(offset + s, tag, size, a.seed)))
-                    self._img_cache[key] = px.pin_memory() if getattr(a, "host_pixels", False) else px.to(self.dev)
+                    put(key, proc(self._synth_image_u8(offset + s, tag, size, a.seed)))
                 return self._img_cache[key]
             return image_of
         if scaling == "weak":
             n = (K + W) * E
+            prefetch(range(self.rank * n, self.rank * n + n))
             cyc = self._evqa_cycles(n, vocab, a.seed + 7919 * self.rank, image_of_factory(self.rank * n))
             warm, timed, first = cyc[:W * E], cyc[W * E:], self.rank * K * E
         else:
             total = total or K * E
             lo, hi = self.shard_range(total, self.rank, self.world)
             stream = self._evqa_cycles(total, vocab, a.seed, None)       # ids only: images are materialised for this rank's block
+            prefetch(range(10 ** 7 + self.rank * W * E, 10 ** 7 + self.rank * W * E + W * E))
+            prefetch(range(lo, hi))
             warm_src = self._evqa_cycles(W * E, vocab, a.seed + 104729 * (self.rank + 1), image_of_factory(10 ** 7 + self.rank * W * E))
             img = image_of_factory(0)
 
@@ -501,6 +532,7 @@ def comm_device(dev):
 def timed_leg(leg, K, W, barrier, use_dist, rank, world, dev, scaling=None, total=None):
     """W untimed warm-up steps, then the timed region (K steps of E cycles per rank, or this rank's block of the `total`-cycle stream)
     bracketed by barrier + synchronize; max over ranks.  -> (elapsed, n_local, n_total, ranks, gathered score rows on rank 0)"""
+    import numpy as np
     import torch
     import torch.distributed as dist
     from devqa_amd import lib
@@ -519,7 +551,8 @@ def timed_leg(leg, K, W, barrier, use_dist, rank, world, dev, scaling=None, tota
     n_it = len(timed)
     P = max(1, int(a.profile_every))
     sample = instrumented_iters(n_it, P, not a.no_pipeline)
-    off = bool(os.environ.get("DEVQA_BENCH_NOPROF"))       # A/B of what the event pairs cost: nothing is instrumented
+    # a plain run carries no event pairs: nothing it reports is read from them (--full does)
+    off = bool(os.environ.get("DEVQA_BENCH_NOPROF")) or not a.full       # (DEVQA_BENCH_NOPROF: A/B of what the event pairs cost under --full)
     PROF["frac"], PROF["steps"] = (len(sample) / n_it, sorted(sample)) if sample else (1.0, list(range(n_it)))
     lib.profile(1)            # new recording
     if sample or off:
@@ -532,6 +565,9 @@ def timed_leg(leg, K, W, barrier, use_dist, rank, world, dev, scaling=None, tota
     barrier()
     elapsed = time.time() - t0
     lib.profile(0)
+    if timed:           # what the last timed step returned to its caller (--dump-outputs): its results, and the FT loop's steps / losses
+        n_last = len(timed[-1][1])
+        leg.last_step = (outs[-n_last:], metas[-n_last:], np.array(leg.be.last_steps), np.array(leg.be.last_losses))
     n_local = len(outs)
     n_total, ranks = n_local, 1
     got = BatchedEditEval.score_rows(outs, metas, first)
@@ -551,6 +587,31 @@ def timed_leg(leg, K, W, barrier, use_dist, rank, world, dev, scaling=None, tota
             assert got.shape == (n_total, 16) and [int(v) for v in got[:, 0]] == list(range(n_total))
     leg.last_batch_sizes = [len(b[1]) for b in timed]
     return elapsed, n_local, n_total, ranks, got
+
+
+def dump_outputs(path, outs, metas, steps, losses):
+    """--dump-outputs: what the last timed step handed back to its caller, as float32 DIR/<name>.npy (well under 1 MB at 127 cycles):
+    accuracy [E, 12] (reliability, text / image rephrase, the 9 locality probes in LOC_ORDER), ft_steps [E], final_loss [E], ft_losses [E, num_steps]
+    (zeros after an early stop), post_edit_tokens [E, 12, L] / pre_edit_tokens [E, 9, L] (the argmax token ids over each probe's label rows after /
+    before the edit, padded with -1).  The per-cycle edit_time is a timing, not an output: left out."""
+    import numpy as np
+    from devqa_amd.batched import BatchedEditEval, LOC_ORDER
+    rows = BatchedEditEval.score_rows(outs, metas, 0)       # [E, 16]: id, 12 accuracies, edit_time, steps, final loss
+    probes = [("reliability", None), ("generality", "text_rephrase"), ("generality", "image_rephrase")] + [("locality", n) for n in LOC_ORDER]
+
+    def tokens(key, sel):
+        ids = [[[int(t) for t in (r[sec][0] if sub is None else r[sec][sub][0])[key].split()] for sec, sub in sel] for r in outs]
+        arr = np.full((len(outs), len(sel), max(len(t) for c in ids for t in c)), -1, np.float32)
+        for i, c in enumerate(ids):
+            for j, t in enumerate(c):
+                arr[i, j, :len(t)] = t
+        return arr
+    arrays = {"accuracy": rows[:, 1:13], "ft_steps": np.asarray(steps, np.float32), "final_loss": rows[:, 15],
+              "ft_losses": np.asarray(losses, np.float32), "post_edit_tokens": tokens("predict_after_edit", probes),
+              "pre_edit_tokens": tokens("predict_before_edit", probes[3:])}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def gemm_roofline(K_E_local, elapsed):
@@ -701,7 +762,8 @@ def main():
     lib.load()
     layers = None if args.layers is None else tuple(int(x) for x in args.layers.split(","))
     E, K, W = args.cycles_per_step, args.steps, args.warmup
-    want_cpu = (not args.no_cpu_baseline) and world == 1
+    full = args.full
+    want_cpu = full and (not args.no_cpu_baseline) and world == 1
 
     def barrier():
         if use_dist:
@@ -718,14 +780,18 @@ def main():
     out = None
     if rank == 0:
         value = n_total / elapsed
-        roof = gemm_roofline(n_local, elapsed)
-        # the deduplicated algorithmic minimum is an upper bound on useful work only when the engine executes at least that much;
-        # with shared prefixes it executes LESS than SURVEY's A_min on this recipe, so the path fraction uses the smaller figure
-        roof["path_frac_of_mfma_peak"] = round(value / world * min(A_MIN_TFLOP_PER_CYCLE, roof["executed_tflop_per_cycle"] or A_MIN_TFLOP_PER_CYCLE)
-                                               / MFMA_PEAK_TFLOPS, 4)
-        roof["profile_dropped_launches"] = lib.profile_dropped()
-        att, ln, ft = side_kernels(leg.be, elapsed)
+        extra = {}
+        if full:        # the figures read from the slot profiler's event pairs of the timed region
+            roof = gemm_roofline(n_local, elapsed)
+            # the deduplicated algorithmic minimum is an upper bound on useful work only when the engine executes at least that much;
+            # with shared prefixes it executes LESS than SURVEY's A_min on this recipe, so the path fraction uses the smaller figure
+            roof["path_frac_of_mfma_peak"] = round(value / world * min(A_MIN_TFLOP_PER_CYCLE, roof["executed_tflop_per_cycle"] or A_MIN_TFLOP_PER_CYCLE)
+                                                   / MFMA_PEAK_TFLOPS, 4)
+            roof["profile_dropped_launches"] = lib.profile_dropped()
+            att, ln, ft = side_kernels(leg.be, elapsed)
+            extra = {"roofline": roof, "roofline_hbm": {"ft_adamw_step": ft}, "kernels": {"attention": att, "layernorm": ln}}
         steps_mean = leg.be.stats["steps"] / max(leg.be.stats["cycles"], 1)
+        npad_mean = leg.be.stats.get("npad_sum", 0) / max(leg.be.stats.get("cycles", 1), 1)
         d_in = leg.cfg["text_config"]["ffn_dim"]
         out = {
             "metric": "edit+eval cycles/sec, BLIP-2 FT_VL EVQA", "value": round(value, 3), "unit": "cycles/s",
@@ -739,17 +805,24 @@ def main():
                                                        "in total, block-partitioned over the ranks" if args.scaling == "strong" else "per GPU",
                                                        max(head_batches) if head_batches else E, DENSE_RECIPE if head_style == "survey" else SPARSE_RECIPE),
                        "ffn": "dense" if head_style == "survey" else "sparse", "cycles_per_step": E, "cycles_total": n_total,
-                       "mean_ft_steps": round(steps_mean, 2), "ft_active_columns_mean": ft["npad_mean"], "ft_columns": d_in,
+                       "mean_ft_steps": round(steps_mean, 2), "ft_active_columns_mean": round(npad_mean, 1), "ft_columns": d_in,
                        "layers": "39/12/32" if layers is None else args.layers, "sharding": "splits block-partitioned, 1 gather"},
-            "roofline": roof,
-            "roofline_hbm": {"ft_adamw_step": ft},
-            "kernels": {"attention": att, "layernorm": ln},
+            **extra,
             "phase_s": {k: round(v, 3) for k, v in leg.be.stats.items() if k.startswith("t_")},
             "build_s": round(leg.build_s, 1),
         }
         if head_style == "survey":
             out["value_survey_recipe"] = out["value"]
-    # ---- the other scaling leg on the same model: both are printed at every N ------------------------------------------------------
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *leg.last_step)
+    if not full:
+        if rank == 0 and args.dump_rows and args.scaling == "strong":
+            import numpy as np
+            np.save(args.dump_rows, head_rows)
+        if rank == 0:
+            print(json.dumps(out))
+        return finish_dist(use_dist)
+    # ---- --full: the other scaling leg on the same model: both are printed at every N -------------------------------------------------
     strong_rows = head_rows if args.scaling == "strong" else None
     if not args.no_second_leg:
         other = "strong" if args.scaling == "weak" else "weak"
@@ -817,7 +890,13 @@ def main():
         else:
             out["cpu_baseline"] = None
         print(json.dumps(out))
+    finish_dist(use_dist)
+
+
+def finish_dist(use_dist):
     if use_dist:
+        import torch
+        import torch.distributed as dist
         from devqa_amd.dist import close_score_comms
         dist.barrier()
         torch.cuda.synchronize()

@@ -66,7 +66,7 @@ def test_bench_walks_the_distributed_branches_with_one_rank():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                DEVQA_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--cycles-per-step", "4", "--layers", "2,2,2", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                        "--cycles-per-step", "4", "--layers", "2,2,2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -93,7 +93,7 @@ def test_two_ranks_share_the_gpu_strong_stream_equals_one_rank(tmp_path):
         env.update(DEVQA_DIST_BACKEND="gloo", DEVQA_BENCH_SHARE_GPU="1")
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--cycles-per-step", "12",
                             "--layers", "2,2,2", "--no-cpu-baseline", "--no-hbm-micro", "--ffn", "sparse", "--scaling", "strong", "--strong-cycles", "24",
-                            "--dump-rows", f], env=env, capture_output=True, text=True, timeout=900)
+                            "--dump-rows", f, "--full"], env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert j["n_gpus"] == n and j["scaling"] == "strong" and j["config"]["cycles_total"] == 24 and j["weak"]["scaling"] == "weak"
