@@ -379,12 +379,6 @@ class BatchedEditEval:
         ev[1].record()
         # ---- 3. frozen decoder prefix ---------------------------------------------------------------
         ps = eng.pack_from_tokens(seqs, img_tokens, share_prefix=self.share_prefix)
-        x_mid, a = eng.decoder_layers(ps, stop_before_fc2=True)
-        d = x_mid.shape[1]
-        b2 = eng.edit_bias()   # None for LLaMA-family decoders
-        wname = self.editor._edit_target()
-        w0 = self.vllm.model.get(wname)               # fp32 master [d, ffn]
-        w0_op = self.vllm.model.weight_for_gemm(wname)  # GEMM operand (bf16 shadow, or the master in fp32 mode)
         # tail rows of every probe, grouped per cycle (contiguous) so each edit's rows form one GEMM
         row_idx, cyc_rows = [], []
         for plist in probes:
@@ -394,9 +388,6 @@ class BatchedEditEval:
                 end = ps.start[p.seq] + ps.length[p.seq]
                 row_idx += list(range(end - p.L, end))
             cyc_rows.append((r0, len(row_idx)))
-        ridx = lib.h2d(row_idx, torch.int32, dev)     # pinned + non-blocking: a pageable copy would park the host behind the queued vision encoder
-        a_tail = lib.gather_rows(a, ridx)                     # operand dtype [R, ffn]
-        resid_tail = lib.gather_rows(x_mid, ridx)             # fp32 [R, d]
         # FT rows
         ft_idx = []
         labels = np.zeros((E, kmax), np.int32)
@@ -410,7 +401,21 @@ class BatchedEditEval:
                     mask[e, j] = 1.0
                 else:
                     ft_idx.append(end - 1)  # padding row: mask 0 -> coef 0 -> no gradient
-        fidx = lib.h2d(ft_idx, torch.int32, dev)
+        # nothing behind the last layer's attention is read outside these rows (~6 % of the pack): the decoder computes it for them alone
+        # and returns compact buffers, which the row lists are renumbered into
+        tail_seg = lib.TailSegments(cyc_rows, eng.adt, dev)     # tables of stage B's grouped post-edit tail
+        keep = sorted(set(row_idx) | set(ft_idx))
+        slot = {r: i for i, r in enumerate(keep)}
+        x_mid, a = eng.decoder_layers(ps, stop_before_fc2=True, keep_rows=keep)
+        d = x_mid.shape[1]
+        b2 = eng.edit_bias()   # None for LLaMA-family decoders
+        wname = self.editor._edit_target()
+        w0 = self.vllm.model.get(wname)               # fp32 master [d, ffn]
+        w0_op = self.vllm.model.weight_for_gemm(wname)  # GEMM operand (bf16 shadow, or the master in fp32 mode)
+        ridx = lib.h2d([slot[r] for r in row_idx], torch.int32, dev)   # pinned + non-blocking: a pageable copy would park the host behind the queued vision encoder
+        a_tail = lib.gather_rows(a, ridx)                     # operand dtype [R, ffn]
+        resid_tail = lib.gather_rows(x_mid, ridx)             # fp32 [R, d]
+        fidx = lib.h2d([slot[r] for r in ft_idx], torch.int32, dev)
         a_ft = lib.gather_rows(a, fidx).to(torch.float32).view(E, kmax, -1).contiguous()
         a_ft = a_ft * lib.h2d(mask, torch.float32, dev).unsqueeze(-1)   # zero the padding rows (plumbing)
         resid_ft = lib.gather_rows(x_mid, fidx)                      # [E*kmax, d] (+ fc2 bias when the model has one)
@@ -428,7 +433,7 @@ class BatchedEditEval:
             act_ev.record()
             act = (idx, cnt, mx, act_ev)
         ev[2].record()
-        return dict(rds=rds, probes=probes, E=E, kmax=kmax, d=d, b2=b2, w0=w0, w0_op=w0_op, cyc_rows=cyc_rows, a_tail=a_tail,
+        return dict(rds=rds, probes=probes, E=E, kmax=kmax, d=d, b2=b2, w0=w0, w0_op=w0_op, cyc_rows=cyc_rows, tail_seg=tail_seg, a_tail=a_tail,
                     resid_tail=resid_tail, a_ft=a_ft, resid_ft=resid_ft, labels=labels, mask=mask, ev=ev, act=act)
 
     @torch.no_grad()
@@ -460,10 +465,13 @@ class BatchedEditEval:
         evb[2].record()
         # ---- 6. post-edit tail:  y_post = y_pre + (dW_e restricted to its active columns) . a -------------
         delta_op = delta_c if eng.adt == torch.float32 else lib.cast_f32_bf16(delta_c)  # [E, d, npad]
-        y_post = y_pre  # updated in place, cycle by cycle
-        for e, (r0, r1) in enumerate(cyc_rows):
-            a_pc = lib.gather_cols(a_tail[r0:r1], idx[e:e + 1], cnt[e:e + 1], npad, per_edit=False)[0]
-            lib.gemm(a_pc, delta_op[e], residual=y_post[r0:r1], out_f32=y_post[r0:r1])
+        y_post = y_pre  # updated in place
+        if lib.gemm_grouped_supported(delta_op.dtype, npad):     # every cycle in two launches; same tile code and K order as the loop below
+            lib.tail_grouped_(a_tail, c["tail_seg"], idx, cnt, npad, delta_op, y_post)
+        else:      # a long K (dense FFN activations): a per-edit GEMM splits K over workgroups, which the grouped kernel does not
+            for e, (r0, r1) in enumerate(cyc_rows):
+                a_pc = lib.gather_cols(a_tail[r0:r1], idx[e:e + 1], cnt[e:e + 1], npad, per_edit=False)[0]
+                lib.gemm(a_pc, delta_op[e], residual=y_post[r0:r1], out_f32=y_post[r0:r1])
         post_argmax = self._argmax_from_y(y_post, "post")
         if self.keep_debug:
             self.debug["delta"] = (delta_c, idx, cnt, npad)

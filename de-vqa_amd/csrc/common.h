@@ -37,6 +37,13 @@ int devqa_fail(int code, const char* fmt, ...);
 int devqa_prof_begin(int slot, hipStream_t st);            // -> handle, or -1 when profiling is off / the pool is full
 void devqa_prof_end(int handle, double work, hipStream_t st);
 
+// library-internal forms of devqa_gemm_bf16 / devqa_gemm_f32 (gemm_bf16.hip, gemm_f32.hip): M rows computed with the kernel family and
+// split-K slicing of an Md-row call (Md >= M), so that each row carries the bits it has in that call
+int devqa_gemm_bf16_as(int Md, const devqa_bf16* A, int64_t lda, const devqa_bf16* W, int64_t ldw, const float* bias, int M, int N, int K,
+                       float alpha, int act, const float* residual, devqa_bf16* out_bf16, float* out_f32, int64_t ldc, void* stream);
+int devqa_gemm_f32_as(int Md, const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N, int K, float alpha,
+                      int act, const float* residual, float* out_f32, int64_t ldc, void* stream);
+
 // dynamic-LDS opt-in above 48 KiB: once per (kernel instantiation, device), safe against concurrent host threads.
 // `done` is a function-local static std::atomic<unsigned> bit mask over device ordinals.
 #include <atomic>

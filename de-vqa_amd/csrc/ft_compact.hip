@@ -95,6 +95,45 @@ extern "C" int devqa_gather_cols_bf16(const devqa_bf16* src, int64_t src_stride_
     return launch_gather_cols<bf16_t>(src, src_stride_e, ld_src, rows, idx, idx_stride_e, count, E, npad, out, stream);
 }
 
+// grouped form: the rows of ONE matrix belong to different edits (row_edit[r]), each row is gathered through its edit's column list:
+//   out[r, c] = c < count[row_edit[r]] ? src[r, idx[row_edit[r], c]] : 0          (the post-edit tail: all cycles in one launch)
+template <typename T>
+__global__ void gather_cols_grouped_kernel(const T* __restrict__ src, int64_t ld_src, int rows, const int32_t* __restrict__ row_edit,
+                                           const int32_t* __restrict__ idx, int64_t idx_stride_e, const int32_t* __restrict__ count, int E,
+                                           int npad, T* __restrict__ out) {
+    const int64_t total = (int64_t)rows * npad;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % npad);
+        const int64_t r = i / npad;
+        const int e = row_edit[r];
+        T v = (T)0;
+        if (e >= 0 && e < E && c < count[e]) v = src[r * ld_src + idx[(int64_t)e * idx_stride_e + c]];
+        out[i] = v;
+    }
+}
+
+template <typename T>
+static int launch_gather_cols_grouped(const T* src, int64_t ld_src, int rows, const int32_t* row_edit, const int32_t* idx, int64_t idx_stride_e,
+                                      const int32_t* count, int E, int npad, T* out, void* stream) {
+    DEVQA_CHECK_ARG(src && row_edit && idx && count && out, "gather_cols_grouped: null pointer");
+    if (E == 0 || rows == 0) return DEVQA_OK;
+    DEVQA_CHECK_SHAPE(E > 0 && rows > 0 && npad > 0 && ld_src > 0, "gather_cols_grouped: bad dims");
+    const int64_t total = (int64_t)rows * npad;
+    const int gx = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(gather_cols_grouped_kernel<T>, dim3(gx), dim3(256), 0, (hipStream_t)stream, src, ld_src, rows, row_edit, idx, idx_stride_e,
+                       count, E, npad, out);
+    DEVQA_LAUNCH_CHECK("gather_cols_grouped");
+    return DEVQA_OK;
+}
+extern "C" int devqa_gather_cols_grouped_f32(const float* src, int64_t ld_src, int rows, const int32_t* row_edit, const int32_t* idx,
+                                             int64_t idx_stride_e, const int32_t* count, int E, int npad, float* out, void* stream) {
+    return launch_gather_cols_grouped<float>(src, ld_src, rows, row_edit, idx, idx_stride_e, count, E, npad, out, stream);
+}
+extern "C" int devqa_gather_cols_grouped_bf16(const devqa_bf16* src, int64_t ld_src, int rows, const int32_t* row_edit, const int32_t* idx,
+                                              int64_t idx_stride_e, const int32_t* count, int E, int npad, devqa_bf16* out, void* stream) {
+    return launch_gather_cols_grouped<bf16_t>(src, ld_src, rows, row_edit, idx, idx_stride_e, count, E, npad, out, stream);
+}
+
 // dense[e or shared][row][idx[e][c]] (+)= compact[e][row][c]  for c < count[e]   (scatter a compacted delta back)
 __global__ void scatter_cols_add_kernel(const float* __restrict__ comp, int rows, const int32_t* __restrict__ idx,
                                         const int32_t* __restrict__ count, int npad, float* __restrict__ dense, int64_t ld_dense) {

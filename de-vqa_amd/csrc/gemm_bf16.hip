@@ -15,11 +15,13 @@
 
 #define BK 64
 
+// One BM x BN output tile at (m0, n0) over the K steps [kb, nk) of BK: the whole tile code, shared by gemm_bf16_tn_kernel and the
+// grouped form below (rows >= M and columns >= N are masked; m0 need not be a multiple of BM).
 template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(
+__device__ __forceinline__ void gemm_bf16_tn_tile(
     const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ W, int64_t ldw,
     const float* __restrict__ bias, int M, int N, int K, float alpha, int act, const float* residual,
-    bf16_t* out_bf16, float* out_f32, int64_t ldc, int tiles_m, int tiles_n, int steps_per_split) {
+    bf16_t* out_bf16, float* out_f32, int64_t ldc, int m0, int n0, int kb, int nk) {
     constexpr int TM = BM / WM / 16;  // 16-row MFMA tiles per wave along M
     constexpr int TN = BN / WN / 16;
     constexpr int A_CHUNKS = BM * (BK / 8) / 256;  // 16-byte chunks per thread per tile
@@ -31,18 +33,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(
     constexpr int A_BYTES = BM * BK * 2;
     constexpr int B_BYTES = BN * BK * 2;
     constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-
-    // ---- XCD-aware tile id: blocks b and b+8 share an XCD; give each XCD a contiguous run ----
-    const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    // m fastest: consecutive blocks walk down M for one N panel (W panel stays L2 resident)
-    const int tile_m = bid % tiles_m;
-    const int tile_n = bid / tiles_m;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -57,11 +47,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(
         for (int j = 0; j < TN; ++j) acc[i][j] = (float4_t){0.f, 0.f, 0.f, 0.f};
 
     uint4 ra[A_CHUNKS], rb[B_CHUNKS];
-    // split-K: blockIdx.y owns K steps [kb, nk) and writes a raw fp32 partial slab (steps_per_split > 0)
-    const int nk_all = (K + BK - 1) / BK;
-    const int kb = steps_per_split > 0 ? (int)blockIdx.y * steps_per_split : 0;
-    const int nk = steps_per_split > 0 ? min(nk_all, kb + steps_per_split) : nk_all;
-    if (steps_per_split > 0) out_f32 += (int64_t)blockIdx.y * M * ldc;
 
     auto gload = [&](int kt) {
         const int k0 = kt * BK;
@@ -156,6 +141,74 @@ __global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(
             }
         }
     }
+}
+
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void gemm_bf16_tn_kernel(
+    const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ W, int64_t ldw,
+    const float* __restrict__ bias, int M, int N, int K, float alpha, int act, const float* residual,
+    bf16_t* out_bf16, float* out_f32, int64_t ldc, int tiles_m, int tiles_n, int steps_per_split) {
+    // ---- XCD-aware tile id: blocks b and b+8 share an XCD; give each XCD a contiguous run ----
+    const int nwg = tiles_m * tiles_n;
+    int bid = blockIdx.x;
+    {
+        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    // m fastest: consecutive blocks walk down M for one N panel (W panel stays L2 resident)
+    const int tile_m = bid % tiles_m;
+    const int tile_n = bid / tiles_m;
+    // split-K: blockIdx.y owns K steps [kb, nk) and writes a raw fp32 partial slab (steps_per_split > 0)
+    const int nk_all = (K + BK - 1) / BK;
+    const int kb = steps_per_split > 0 ? (int)blockIdx.y * steps_per_split : 0;
+    const int nk = steps_per_split > 0 ? min(nk_all, kb + steps_per_split) : nk_all;
+    if (steps_per_split > 0) out_f32 += (int64_t)blockIdx.y * M * ldc;
+    gemm_bf16_tn_tile<BM, BN, WM, WN>(A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, tile_m * BM, tile_n * BN, kb, nk);
+}
+
+// ---- grouped form (the post-edit tail of the batched FT_VL evaluation): every row tile has its OWN weight matrix.  tab: int32
+// [n_mt][3] = (edit e, first row m0, end row m1 of e's segment) per row tile; rows [m0, min(m0 + BM, m1)) of y += A . W_e^T.  Same
+// tile code, same K order as one gemm_bf16_tn_kernel launch per edit: same bits.
+template <int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void gemm_bf16_tn_grouped_kernel(
+    const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ W, int64_t ldw, int64_t w_stride_e, const int32_t* __restrict__ tab,
+    int n_mt, int E, int R, int N, int K, float* y, int64_t ldc) {
+    const int t = blockIdx.x % n_mt, tile_n = blockIdx.x / n_mt;     // m fastest: the edits of one column panel side by side
+    const int e = tab[3 * t], m0 = tab[3 * t + 1], m1 = tab[3 * t + 2];
+    if (e < 0 || e >= E || m0 < 0 || m1 > R || m0 >= m1) return;    // (uniform per workgroup)
+    gemm_bf16_tn_tile<BM, BN, WM, WN>(A, lda, W + (int64_t)e * w_stride_e, ldw, nullptr, m1, N, K, 1.0f, 0, y, nullptr, y, ldc, m0, tile_n * BN, 0,
+                                      (K + BK - 1) / BK);
+}
+
+extern "C" int devqa_gemm_grouped_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf16* W, int64_t ldw, int64_t w_stride_e, const int32_t* tile_tab,
+                                       int n_tiles, int bm, int E, int R, int N, int K, float* y, int64_t ldc, void* stream) {
+    DEVQA_CHECK_ARG(A && W && tile_tab && y, "gemm_grouped: null pointer");
+    if (n_tiles == 0 || N == 0) return DEVQA_OK;
+    DEVQA_CHECK_ARG(bm == 32 || bm == 64, "gemm_grouped: row tile %d (32 or 64)", bm);
+    DEVQA_CHECK_SHAPE(n_tiles > 0 && E > 0 && R > 0 && N > 0 && K > 0, "gemm_grouped: bad dims");
+    DEVQA_CHECK_SHAPE(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && w_stride_e % 8 == 0 && lda >= K && ldw >= K && ldc >= N,
+                      "gemm_grouped: K / leading dims must be multiples of 8 and cover the matrices");
+    DEVQA_CHECK_SHAPE((((uintptr_t)A) & 15) == 0 && (((uintptr_t)W) & 15) == 0, "gemm_grouped: operands must be 16-byte aligned");
+    // one launch per edit would split a long K over workgroups (devqa_gemm_bf16's small-M rule, from 8 K steps on): not this kernel's order
+    DEVQA_CHECK_SHAPE(devqa_gemm_grouped_supported(DEVQA_DTYPE_BF16, K), "gemm_grouped: K=%d takes the split-K path per edit", K);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles_n = (N + 127) / 128;
+    const size_t smem = 2 * (size_t)(bm + 128) * BK * 2;
+    if (bm == 32)
+        hipLaunchKernelGGL((gemm_bf16_tn_grouped_kernel<32, 128, 1, 4>), dim3(n_tiles * tiles_n), dim3(256), smem, st, A, lda, W, ldw, w_stride_e,
+                           tile_tab, n_tiles, E, R, N, K, y, ldc);
+    else
+        hipLaunchKernelGGL((gemm_bf16_tn_grouped_kernel<64, 128, 2, 2>), dim3(n_tiles * tiles_n), dim3(256), smem, st, A, lda, W, ldw, w_stride_e,
+                           tile_tab, n_tiles, E, R, N, K, y, ldc);
+    DEVQA_LAUNCH_CHECK("gemm_grouped");
+    return DEVQA_OK;
+}
+
+// 1 when one devqa_gemm_bf16 / devqa_gemm_f32 call per edit (few rows, reduction length K) sums K in ONE k-ordered chain -- the order of
+// the grouped kernels -- whatever its row count: below the split-K rules of the two dispatchers
+extern "C" int devqa_gemm_grouped_supported(int dtype, int K) {
+    if (dtype == DEVQA_DTYPE_BF16) return K > 0 && K % 8 == 0 && (K + BK - 1) / BK / 4 < 2;
+    return dtype == DEVQA_DTYPE_F32 && K > 0 && K % 4 == 0 && K < 2048;
 }
 
 #include <mutex>
@@ -351,7 +404,17 @@ extern "C" int devqa_gemm_bf16_swiglu_supported(int M, int N, int K) {
 extern "C" int devqa_gemm_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf16* W, int64_t ldw, const float* bias,
                                int M, int N, int K, float alpha, int act, const float* residual, devqa_bf16* out_bf16,
                                float* out_f32, int64_t ldc, void* stream) {
+    return devqa_gemm_bf16_as(M, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, stream);
+}
+
+// devqa_gemm_bf16 on M rows with every dispatch decision (kernel family, split-K slicing) taken as for Md >= M rows: a row of the
+// result then has the bits the same row has in an Md-row call -- the K order of an output element depends on the kernel and the
+// slicing, never on its tile-mates (devqa_llm_prefix_rows: the kept rows of the last layer)
+int devqa_gemm_bf16_as(int Md, const devqa_bf16* A, int64_t lda, const devqa_bf16* W, int64_t ldw, const float* bias,
+                       int M, int N, int K, float alpha, int act, const float* residual, devqa_bf16* out_bf16,
+                       float* out_f32, int64_t ldc, void* stream) {
     DEVQA_CHECK_ARG(A && W, "gemm: null operand");
+    DEVQA_CHECK_ARG(Md >= M, "gemm: dispatch rows %d < rows %d", Md, M);
     DEVQA_CHECK_ARG(out_bf16 || out_f32, "gemm: no output");
     DEVQA_CHECK_ARG(act >= 0 && act <= DEVQA_ACT_SWIGLU_IL16, "gemm: bad act %d", act);
     if (M == 0 || N == 0) return DEVQA_OK;
@@ -363,7 +426,7 @@ extern "C" int devqa_gemm_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf1
     hipStream_t st = (hipStream_t)stream;
     const int g_gemm_mode = gemm_mode();
     if (act == DEVQA_ACT_SWIGLU_IL16) {      // fused SwiGLU: the 256 x 256 kernel only (devqa_gemm_bf16_swiglu_supported says when)
-        if (!devqa_gemm_bf16_swiglu_supported(M, N, K)) return devqa_fail(DEVQA_E_SHAPE, "gemm_bf16: fused SwiGLU is not available for M=%d N=%d K=%d in this mode", M, N, K);
+        if (!devqa_gemm_bf16_swiglu_supported(Md, N, K)) return devqa_fail(DEVQA_E_SHAPE, "gemm_bf16: fused SwiGLU is not available for M=%d N=%d K=%d in this mode", M, N, K);
         const int ph = devqa_prof_begin(3, st);
         const int rc = launch_gemm_pp(g_gemm_mode >= 20 ? g_gemm_mode - 20 : 2, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
         devqa_prof_end(ph, 2.0 * (double)M * (double)N * (double)K, st);
@@ -377,17 +440,17 @@ extern "C" int devqa_gemm_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf1
         const char* e = getenv("DEVQA_SPLITK_MAXM");
         splitk_max_m = e ? atoi(e) : 1024;
     }
-    if (M <= splitk_max_m && g_gemm_mode == 0 && N % 4 == 0 && ldc % 4 == 0 &&
+    if (Md <= splitk_max_m && g_gemm_mode == 0 && N % 4 == 0 && ldc % 4 == 0 &&
         ((((uintptr_t)out_f32) | ((uintptr_t)residual) | ((uintptr_t)bias)) & 15) == 0 && (((uintptr_t)out_bf16) & 7) == 0) {
-        const int bm = M <= 64 ? 64 : 128;
+        const int bm = Md <= 64 ? 64 : 128;
         const int tiles_m = (M + bm - 1) / bm, tiles_n = (N + 127) / 128, nk = (K + BK - 1) / BK;
-        const int tiles = tiles_m * tiles_n;
-        int splits = (M <= 64 || tiles < 128) ? 512 / tiles : 1;
+        const int tiles = tiles_m * tiles_n, tiles_d = (Md + bm - 1) / bm * tiles_n;     // launched / deciding
+        int splits = (Md <= 64 || tiles_d < 128) ? 512 / tiles_d : 1;
         if (splits > nk / 4) splits = nk / 4;
         if (splits >= 2) {
             const int steps = (nk + splits - 1) / splits;
             const int used = (nk + steps - 1) / steps;
-            float* ws = splitk_workspace(st, (size_t)used * M * N * sizeof(float));
+            float* ws = splitk_workspace(st, (size_t)used * Md * N * sizeof(float));
             if (ws) {
                 if (bm == 64) {
                     auto kern = gemm_bf16_tn_kernel<64, 128, 2, 2>;
@@ -409,7 +472,7 @@ extern "C" int devqa_gemm_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf1
             }
         }
     }
-    if (M <= 32) return launch_gemm<32, 128, 1, 4>(A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
+    if (Md <= 32) return launch_gemm<32, 128, 1, 4>(A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
     // mode 0: LDS-DMA staging when K % 64 == 0, 256x256 tiles for large problems (default); 1: force the
     // register-staged kernels; 2: LDS-DMA staging but no 256x256 tiles; 10..17: experimental ring variants
     // (A/B testing via devqa_gemm_set_mode / DEVQA_GEMM)
@@ -417,14 +480,14 @@ extern "C" int devqa_gemm_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf1
     const bool vec_ok = (N % 4 == 0) && (ldc % 4 == 0) && ((((uintptr_t)out_f32) | ((uintptr_t)residual) | ((uintptr_t)bias)) & 15) == 0 &&
                         (((uintptr_t)out_bf16) & 7) == 0;
     const bool glds = (K % 64 == 0) && g_gemm_mode != 1 && vec_ok;
-    if (glds && g_gemm_mode >= 20 && M > 64)  // 256x256 ping-pong variants (gemm_bf16_pp.hip)
+    if (glds && g_gemm_mode >= 20 && Md > 64)  // 256x256 ping-pong variants (gemm_bf16_pp.hip)
         return launch_gemm_pp(g_gemm_mode - 20, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
-    if (glds && g_gemm_mode >= 10 && M > 64)  // experimental N-stage ring variants (gemm_bf16_pipe.hip)
+    if (glds && g_gemm_mode >= 10 && Md > 64)  // experimental N-stage ring variants (gemm_bf16_pipe.hip)
         return launch_gemm_pipe(g_gemm_mode - 10, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
-    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+    const long t128 = (long)((Md + 127) / 128) * ((N + 127) / 128);
+    const long t256 = (long)((Md + 255) / 256) * ((N + 255) / 256);
     int variant;  // 1: 64x128, 2: 128x128, 3: 256x256 ping-pong (gemm_bf16_pp.hip; mode 3 = the simple 2-stage 256x256 ring)
-    if (M <= 64 || t128 < 384) variant = 1;
+    if (Md <= 64 || t128 < 384) variant = 1;
     else if (glds && g_gemm_mode != 2 && t256 >= 128) variant = 3;
     else variant = 2;
     if (!glds) {
@@ -436,7 +499,7 @@ extern "C" int devqa_gemm_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf1
     int rc;
     if (variant == 1) rc = launch_gemm_glds_64x128(A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
     else if (variant == 2) rc = launch_gemm_glds_128x128(A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
-    else if (g_gemm_mode == 3 || (int64_t)M * lda * 2 >= (1ll << 32) || (int64_t)N * ldw * 2 >= (1ll << 32))  // mode 3: previous default
+    else if (g_gemm_mode == 3 || (int64_t)Md * lda * 2 >= (1ll << 32) || (int64_t)N * ldw * 2 >= (1ll << 32))  // mode 3: previous default
         rc = launch_gemm_pipe(7, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
     else rc = launch_gemm_pp(2, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_bf16, out_f32, ldc, st);
     devqa_prof_end(ph, 2.0 * (double)M * (double)N * (double)K, st);

@@ -14,20 +14,13 @@ void devqa_launch_splitk_reduce_epilogue(const float* ws, int splits, int M, int
 #define F_BK 32
 #define F_LD 34
 
-__global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restrict__ A, int64_t lda,
-                                                          const float* __restrict__ W, int64_t ldw,
-                                                          const float* __restrict__ bias, int M, int N, int K, float alpha,
-                                                          int act, const float* residual, float* out_f32, int64_t ldc,
-                                                          int tiles_m, int k_per_split) {
+// One 64 x 64 output tile at (m0, n0) over K range [kb, ke): the whole tile code, shared by gemm_f32_tn_kernel and the grouped form
+// (rows >= M and columns >= N are masked; m0 need not be a multiple of 64).  raw: split-K partial, no epilogue.
+__device__ __forceinline__ void gemm_f32_tn_tile(const float* __restrict__ A, int64_t lda, const float* __restrict__ W, int64_t ldw,
+                                                 const float* __restrict__ bias, int M, int N, float alpha, int act, const float* residual,
+                                                 float* out_f32, int64_t ldc, int m0, int n0, int kb, int ke, int k_per_split) {
     __shared__ float As[64 * F_LD];
     __shared__ float Bs[64 * F_LD];
-    const int tile_m = blockIdx.x % tiles_m, tile_n = blockIdx.x / tiles_m;
-    const int m0 = tile_m * 64, n0 = tile_n * 64;
-    // split-K (k_per_split > 0): blockIdx.y owns K range [kb, ke) and writes a raw fp32 partial slab [M][ldc]; the reduce pass sums the
-    // slabs in slice order (deterministic) and applies the epilogue
-    const int kb = k_per_split > 0 ? (int)blockIdx.y * k_per_split : 0;
-    const int ke = k_per_split > 0 ? min(K, kb + k_per_split) : K;
-    if (k_per_split > 0) out_f32 += (int64_t)blockIdx.y * M * ldc;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fq = lane >> 4;
     float4_t acc[4];
@@ -98,10 +91,57 @@ __global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restric
     }
 }
 
+__global__ __launch_bounds__(256) void gemm_f32_tn_kernel(const float* __restrict__ A, int64_t lda,
+                                                          const float* __restrict__ W, int64_t ldw,
+                                                          const float* __restrict__ bias, int M, int N, int K, float alpha,
+                                                          int act, const float* residual, float* out_f32, int64_t ldc,
+                                                          int tiles_m, int k_per_split) {
+    const int tile_m = blockIdx.x % tiles_m, tile_n = blockIdx.x / tiles_m;
+    // split-K (k_per_split > 0): blockIdx.y owns K range [kb, ke) and writes a raw fp32 partial slab [M][ldc]; the reduce pass sums the
+    // slabs in slice order (deterministic) and applies the epilogue
+    const int kb = k_per_split > 0 ? (int)blockIdx.y * k_per_split : 0;
+    const int ke = k_per_split > 0 ? min(K, kb + k_per_split) : K;
+    if (k_per_split > 0) out_f32 += (int64_t)blockIdx.y * M * ldc;
+    gemm_f32_tn_tile(A, lda, W, ldw, bias, M, N, alpha, act, residual, out_f32, ldc, tile_m * 64, tile_n * 64, kb, ke, k_per_split);
+}
+
+// grouped form: see gemm_bf16_tn_grouped_kernel (gemm_bf16.hip); tab: int32 [n_mt][3] = (edit, first row, end row of its segment)
+__global__ __launch_bounds__(256) void gemm_f32_tn_grouped_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ W, int64_t ldw,
+                                                                  int64_t w_stride_e, const int32_t* __restrict__ tab, int n_mt, int E, int R, int N,
+                                                                  int K, float* y, int64_t ldc) {
+    const int t = blockIdx.x % n_mt, tile_n = blockIdx.x / n_mt;
+    const int e = tab[3 * t], m0 = tab[3 * t + 1], m1 = tab[3 * t + 2];
+    if (e < 0 || e >= E || m0 < 0 || m1 > R || m0 >= m1) return;    // (uniform per workgroup)
+    gemm_f32_tn_tile(A, lda, W + (int64_t)e * w_stride_e, ldw, nullptr, m1, N, 1.0f, 0, y, y, ldc, m0, tile_n * 64, 0, K, 0);
+}
+
+extern "C" int devqa_gemm_grouped_f32(const float* A, int64_t lda, const float* W, int64_t ldw, int64_t w_stride_e, const int32_t* tile_tab, int n_tiles,
+                                      int bm, int E, int R, int N, int K, float* y, int64_t ldc, void* stream) {
+    DEVQA_CHECK_ARG(A && W && tile_tab && y, "gemm_grouped_f32: null pointer");
+    if (n_tiles == 0 || N == 0) return DEVQA_OK;
+    DEVQA_CHECK_ARG(bm == 64, "gemm_grouped_f32: row tile %d (64)", bm);
+    DEVQA_CHECK_SHAPE(n_tiles > 0 && E > 0 && R > 0 && N > 0 && K > 0, "gemm_grouped_f32: bad dims");
+    DEVQA_CHECK_SHAPE(K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && w_stride_e % 4 == 0 && lda >= K && ldw >= K && ldc >= N,
+                      "gemm_grouped_f32: K / leading dims must be multiples of 4 and cover the matrices");
+    DEVQA_CHECK_SHAPE((((uintptr_t)A) & 15) == 0 && (((uintptr_t)W) & 15) == 0, "gemm_grouped_f32: operands must be 16-byte aligned");
+    DEVQA_CHECK_SHAPE(devqa_gemm_grouped_supported(DEVQA_DTYPE_F32, K), "gemm_grouped_f32: K=%d takes the split-K path per edit", K);
+    hipLaunchKernelGGL(gemm_f32_tn_grouped_kernel, dim3(n_tiles * ((N + 63) / 64)), dim3(256), 0, (hipStream_t)stream, A, lda, W, ldw, w_stride_e,
+                       tile_tab, n_tiles, E, R, N, K, y, ldc);
+    DEVQA_LAUNCH_CHECK("gemm_grouped_f32");
+    return DEVQA_OK;
+}
+
 extern "C" int devqa_gemm_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N,
                               int K, float alpha, int act, const float* residual, float* out_f32, int64_t ldc,
                               void* stream) {
+    return devqa_gemm_f32_as(M, A, lda, W, ldw, bias, M, N, K, alpha, act, residual, out_f32, ldc, stream);
+}
+
+// devqa_gemm_f32 on M rows with the split-K decision and slicing of an Md-row call (Md >= M): same bits per row as that call
+int devqa_gemm_f32_as(int Md, const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, int M, int N,
+                      int K, float alpha, int act, const float* residual, float* out_f32, int64_t ldc, void* stream) {
     DEVQA_CHECK_ARG(A && W && out_f32, "gemm_f32: null pointer");
+    DEVQA_CHECK_ARG(Md >= M, "gemm_f32: dispatch rows %d < rows %d", Md, M);
     DEVQA_CHECK_ARG(act >= 0 && act <= 3, "gemm_f32: bad act %d", act);
     if (M == 0 || N == 0) return DEVQA_OK;
     DEVQA_CHECK_SHAPE(M > 0 && N > 0 && K > 0, "gemm_f32: bad dims %d %d %d", M, N, K);
@@ -113,15 +153,15 @@ extern "C" int devqa_gemm_f32(const float* A, int64_t lda, const float* W, int64
     // few rows x a long K (the MEND hyper-network: [n <= 64 x 12800] . [1920 x 12800]^T streams 98 MB of fp32 weights through
     // 30 workgroups): split K over enough workgroups to fill the chip; slabs are summed in slice order, so the result is
     // deterministic (it is no longer ONE k-ordered fmaf chain: partial chains of k_per_split terms, then their ordered sum)
-    const int tiles = tiles_m * tiles_n;
-    if (M <= 128 && tiles < 128 && K >= 2048 && N % 4 == 0 && ldc % 4 == 0 &&
+    const int tiles = tiles_m * tiles_n, tiles_d = (Md + 63) / 64 * tiles_n;     // launched / deciding
+    if (Md <= 128 && tiles_d < 128 && K >= 2048 && N % 4 == 0 && ldc % 4 == 0 &&
         ((((uintptr_t)out_f32) | ((uintptr_t)residual) | ((uintptr_t)bias)) & 15) == 0) {
-        int splits = 512 / tiles;
+        int splits = 512 / tiles_d;
         if (splits > K / 512) splits = K / 512;
         if (splits >= 2) {
             int kper = ((K + splits - 1) / splits + F_BK - 1) / F_BK * F_BK;
             const int used = (K + kper - 1) / kper;
-            float* ws = devqa_splitk_workspace(st, (size_t)used * M * N * sizeof(float));
+            float* ws = devqa_splitk_workspace(st, (size_t)used * Md * N * sizeof(float));
             if (ws) {
                 hipLaunchKernelGGL(gemm_f32_tn_kernel, dim3(tiles, used), dim3(256), 0, st, A, lda, W, ldw, (const float*)nullptr, M, N, K,
                                    1.0f, 0, (const float*)nullptr, ws, (int64_t)N, tiles_m, kper);

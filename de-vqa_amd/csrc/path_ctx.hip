@@ -97,9 +97,10 @@ int need(const Ctx& c, const std::string& name, const Weight** out, int dtype) {
 }
 int op_dtype(const Ctx& c) { return c.bf16 ? DEVQA_DTYPE_BF16 : DEVQA_DTYPE_F32; }
 
-// out_act: operand-dtype output (bf16 or fp32), out_f32: fp32 output (bf16 mode may write both)
-int gemm(const Ctx& c, const void* A, int64_t lda, const std::string& wname, const char* bname, int M, int N, int K, float alpha, int act,
-         const float* residual, void* out_act, float* out_f32, hipStream_t st) {
+// out_act: operand-dtype output (bf16 or fp32), out_f32: fp32 output (bf16 mode may write both).  Md >= M: the row count the kernel
+// dispatch is taken for (devqa_gemm_bf16_as)
+int gemm_as(const Ctx& c, int Md, const void* A, int64_t lda, const std::string& wname, const char* bname, int M, int N, int K, float alpha,
+            int act, const float* residual, void* out_act, float* out_f32, hipStream_t st) {
     const Weight *W = nullptr, *B = nullptr;
     if (c.bf16) W = find(c, wname + "#shadow");      // an fp32 edit target: GEMMs read its compute-dtype shadow
     if (!W) RC(need(c, wname, &W, op_dtype(c)));
@@ -109,10 +110,14 @@ int gemm(const Ctx& c, const void* A, int64_t lda, const std::string& wname, con
                           (long long)W->shape[1], N, K);
     const float* bias = B ? (const float*)B->ptr : nullptr;
     if (c.bf16)
-        return devqa_gemm_bf16((const devqa_bf16*)A, lda, (const devqa_bf16*)W->ptr, K, bias, M, N, K, alpha, act, residual,
-                               (devqa_bf16*)out_act, out_f32, N, st);
+        return devqa_gemm_bf16_as(Md, (const devqa_bf16*)A, lda, (const devqa_bf16*)W->ptr, K, bias, M, N, K, alpha, act, residual,
+                                  (devqa_bf16*)out_act, out_f32, N, st);
     float* o = out_f32 ? out_f32 : (float*)out_act;
-    return devqa_gemm_f32((const float*)A, lda, (const float*)W->ptr, K, bias, M, N, K, alpha, act, residual, o, N, st);
+    return devqa_gemm_f32_as(Md, (const float*)A, lda, (const float*)W->ptr, K, bias, M, N, K, alpha, act, residual, o, N, st);
+}
+int gemm(const Ctx& c, const void* A, int64_t lda, const std::string& wname, const char* bname, int M, int N, int K, float alpha, int act,
+         const float* residual, void* out_act, float* out_f32, hipStream_t st) {
+    return gemm_as(c, M, A, lda, wname, bname, M, N, K, alpha, act, residual, out_act, out_f32, st);
 }
 
 int layernorm(const Ctx& c, const float* x, const float* add, const std::string& prefix, int M, int D, float eps, void* out_act,
@@ -475,6 +480,19 @@ namespace {
 struct LlmPlan {
     void *h, *qkv, *att, *a, *gu;
 };
+// the rows of the LAST layer that the caller reads (devqa_llm_prefix_rows): everything behind the attention runs on these alone
+struct KeepRows {
+    const int32_t* idx;     // device int32 [n]
+    int n;
+    float* resid;           // out: fp32 [n, d]
+    void *att, *h, *gu;     // scratch: [n, d], [n, d], [n, 2 ffn] (LLaMA) in the operand dtype
+};
+void plan_keep(const Ctx& c, int n_keep, Arena& ar, KeepRows& k) {
+    const int64_t e = esz(c), d = c.d.t_hidden;
+    k.att = ar.take((int64_t)n_keep * d * e);
+    k.h = ar.take((int64_t)n_keep * d * e);
+    k.gu = llama_dec(c) ? ar.take((int64_t)n_keep * 2 * c.d.t_ffn * e) : nullptr;
+}
 int64_t plan_llm(const Ctx& c, int R, bool own_a, Arena& ar, LlmPlan& p) {
     const int64_t e = esz(c), d = c.d.t_hidden;
     p.h = ar.take((int64_t)R * d * e);
@@ -488,7 +506,7 @@ int64_t plan_llm(const Ctx& c, int R, bool own_a, Arena& ar, LlmPlan& p) {
 // biases) in place on x; positions: int32 [R] rotary position of every row.  R/editor/vllms_for_edit/llava/llava.py:63-68,
 // .../minigpt4/minigpt4.py:63-68.
 int llama_layers(const Ctx& c, float* x, const int32_t* pos, const int32_t* desc, int n_seq, int max_len, int R, int dense, int first, int n_layers,
-                 int stop_before_fc2, void* a_out, LlmPlan& w, hipStream_t st) {
+                 int stop_before_fc2, void* a_out, LlmPlan& w, hipStream_t st, const KeepRows* keep = nullptr) {
     const auto& d = c.d;
     const int D = d.t_hidden, H = d.t_heads, dh = D / H, F = d.t_ffn;
     const int64_t e = esz(c);
@@ -504,22 +522,33 @@ int llama_layers(const Ctx& c, float* x, const int32_t* pos, const int32_t* desc
         if (!dense && hipMemsetAsync(w.att, 0, (size_t)R * D * e, st) != hipSuccess) return devqa_fail(DEVQA_E_HIP, "llm_layers: memset failed");
         const char* qkv = (const char*)w.qkv;
         RC(attention(c, qkv, 3 * D, qkv + (int64_t)D * e, 3 * D, qkv + (int64_t)2 * D * e, 3 * D, w.att, D, desc, n_seq, max_len, H, dh, 1, st));
-        RC(gemm(c, w.att, D, p + "self_attn.o_proj.weight", nullptr, R, D, D, 1.f, DEVQA_ACT_NONE, x, nullptr, x, st));
-        RC(rmsnorm(c, x, nullptr, p + "post_attention_layernorm.weight", R, D, d.t_rms_eps, w.h, nullptr, st));
         const bool last_stop = stop_before_fc2 && i == first + n_layers - 1;
+        // the kept rows of the stopping layer: same kernels and dispatch as the all-rows schedule below (gemm_as with Md = R), on n rows
+        const bool kept = last_stop && keep;
+        const int Rl = kept ? keep->n : R;
+        float* xl = kept ? keep->resid : x;
+        const void *attl = w.att, *hl = w.h;
+        void* gul = w.gu;
+        if (kept) {
+            RC(devqa_gather_rows(w.att, keep->idx, Rl, D, (int)e, keep->att, st));
+            RC(devqa_gather_rows(x, keep->idx, Rl, D, 4, xl, st));
+            attl = keep->att; hl = keep->h; gul = keep->gu;
+        }
+        RC(gemm_as(c, R, attl, D, p + "self_attn.o_proj.weight", nullptr, Rl, D, D, 1.f, DEVQA_ACT_NONE, xl, nullptr, xl, st));
+        RC(rmsnorm(c, xl, nullptr, p + "post_attention_layernorm.weight", Rl, D, d.t_rms_eps, (void*)hl, nullptr, st));
         void* a = last_stop ? a_out : w.a;
         // SwiGLU inside the [gate | up] GEMM's epilogue when the host asked for it (t_flags), registered the row-interleaved operand and the
         // call shape takes the 256 x 256 kernel: no [R, 2F] intermediate, no second pass (2.7 GB per layer at R = 40 k, F = 11008)
         snprintf(buf, sizeof(buf), "derived.llama_gu_il.%d.weight", i);
         const Weight* wil = (c.bf16 && (d.t_flags & DEVQA_DESC_FUSE_SWIGLU)) ? find(c, buf) : nullptr;
         if (wil && wil->dtype == DEVQA_DTYPE_BF16 && devqa_gemm_bf16_swiglu_supported(R, 2 * F, D)) {
-            RC(devqa_gemm_bf16((const devqa_bf16*)w.h, D, (const devqa_bf16*)wil->ptr, D, nullptr, R, 2 * F, D, 1.f, DEVQA_ACT_SWIGLU_IL16, nullptr,
-                               (devqa_bf16*)a, nullptr, F, st));
+            RC(devqa_gemm_bf16_as(R, (const devqa_bf16*)hl, D, (const devqa_bf16*)wil->ptr, D, nullptr, Rl, 2 * F, D, 1.f, DEVQA_ACT_SWIGLU_IL16,
+                                  nullptr, (devqa_bf16*)a, nullptr, F, st));
         } else {
             snprintf(buf, sizeof(buf), "derived.llama_gu.%d.weight", i);
-            RC(gemm(c, w.h, D, buf, nullptr, R, 2 * F, D, 1.f, DEVQA_ACT_NONE, nullptr, w.gu, nullptr, st));
-            if (c.bf16) RC(devqa_swiglu_bf16((const devqa_bf16*)w.gu, R, F, (devqa_bf16*)a, st));
-            else RC(devqa_swiglu_f32((const float*)w.gu, R, F, (float*)a, st));
+            RC(gemm_as(c, R, hl, D, buf, nullptr, Rl, 2 * F, D, 1.f, DEVQA_ACT_NONE, nullptr, gul, nullptr, st));
+            if (c.bf16) RC(devqa_swiglu_bf16((const devqa_bf16*)gul, Rl, F, (devqa_bf16*)a, st));
+            else RC(devqa_swiglu_f32((const float*)gul, Rl, F, (float*)a, st));
         }
         if (last_stop) return DEVQA_OK;
         RC(gemm(c, a, F, p + "mlp.down_proj.weight", nullptr, R, D, F, 1.f, DEVQA_ACT_NONE, x, nullptr, x, st));
@@ -527,8 +556,8 @@ int llama_layers(const Ctx& c, float* x, const int32_t* pos, const int32_t* desc
     return DEVQA_OK;
 }
 int llm_layers(const Ctx& c, float* x, const int32_t* pos, const int32_t* desc, int n_seq, int max_len, int R, int dense, int first, int n_layers,
-               int stop_before_fc2, void* a_out, LlmPlan& w, hipStream_t st) {
-    if (llama_dec(c)) return llama_layers(c, x, pos, desc, n_seq, max_len, R, dense, first, n_layers, stop_before_fc2, a_out, w, st);
+               int stop_before_fc2, void* a_out, LlmPlan& w, hipStream_t st, const KeepRows* keep = nullptr) {
+    if (llama_dec(c)) return llama_layers(c, x, pos, desc, n_seq, max_len, R, dense, first, n_layers, stop_before_fc2, a_out, w, st, keep);
     const auto& d = c.d;
     const int D = d.t_hidden, H = d.t_heads, dh = D / H, F = d.t_ffn;
     const int64_t e = esz(c);
@@ -543,11 +572,23 @@ int llm_layers(const Ctx& c, float* x, const int32_t* pos, const int32_t* desc, 
         if (!dense && hipMemsetAsync(w.att, 0, (size_t)R * D * e, st) != hipSuccess) return devqa_fail(DEVQA_E_HIP, "llm_layers: memset failed");
         const char* qkv = (const char*)w.qkv;
         RC(attention(c, qkv, 3 * D, qkv + (int64_t)D * e, 3 * D, qkv + (int64_t)2 * D * e, 3 * D, w.att, D, desc, n_seq, max_len, H, dh, 1, st));
-        RC(gemm(c, w.att, D, p + "self_attn.out_proj.weight", (p + "self_attn.out_proj.bias").c_str(), R, D, D, 1.f, DEVQA_ACT_NONE, x, nullptr, x, st));
-        RC(layernorm(c, x, nullptr, p + "final_layer_norm", R, D, d.t_ln_eps, w.h, nullptr, st));
         const bool last_stop = stop_before_fc2 && i == first + n_layers - 1;
+        // the kept rows of the stopping layer: same kernels and dispatch as the all-rows schedule (gemm_as with Md = R), on n rows
+        const bool kept = last_stop && keep;
+        const int Rl = kept ? keep->n : R;
+        float* xl = kept ? keep->resid : x;
+        const void* attl = w.att;
+        void* hl = w.h;
+        if (kept) {
+            RC(devqa_gather_rows(w.att, keep->idx, Rl, D, (int)e, keep->att, st));
+            RC(devqa_gather_rows(x, keep->idx, Rl, D, 4, xl, st));
+            attl = keep->att; hl = keep->h;
+        }
+        RC(gemm_as(c, R, attl, D, p + "self_attn.out_proj.weight", (p + "self_attn.out_proj.bias").c_str(), Rl, D, D, 1.f, DEVQA_ACT_NONE, xl, nullptr,
+                   xl, st));
+        RC(layernorm(c, xl, nullptr, p + "final_layer_norm", Rl, D, d.t_ln_eps, hl, nullptr, st));
         void* a = last_stop ? a_out : w.a;
-        RC(gemm(c, w.h, D, p + "fc1.weight", (p + "fc1.bias").c_str(), R, F, D, 1.f, DEVQA_ACT_RELU, nullptr, a, nullptr, st));
+        RC(gemm_as(c, R, hl, D, p + "fc1.weight", (p + "fc1.bias").c_str(), Rl, F, D, 1.f, DEVQA_ACT_RELU, nullptr, a, nullptr, st));
         if (last_stop) return DEVQA_OK;
         RC(gemm(c, a, F, p + "fc2.weight", (p + "fc2.bias").c_str(), R, D, F, 1.f, DEVQA_ACT_NONE, x, nullptr, x, st));
     }
@@ -596,6 +637,46 @@ extern "C" int devqa_llm_layers_ex(devqa_ctx_t h, float* x, const int32_t* posit
 extern "C" int devqa_llm_layers(devqa_ctx_t h, float* x, const int32_t* seq_desc, int n_seq, int max_len, int R, int dense, int n_layers,
                                 int stop_before_fc2, void* out_fc2_in, void* workspace, int64_t ws_bytes, void* stream) {
     return devqa_llm_layers_ex(h, x, nullptr, seq_desc, n_seq, max_len, R, dense, 0, n_layers, stop_before_fc2, out_fc2_in, workspace, ws_bytes, stream);
+}
+
+// The frozen prefix for a caller that reads only some rows of it: see include/devqa.h
+extern "C" int64_t devqa_llm_prefix_rows_workspace(devqa_ctx_t h, int R, int n_keep) {
+    Ctx* c = ctx_of(h);
+    if (!c || R <= 0 || n_keep <= 0 || n_keep > R) return -1;
+    Arena a(nullptr, 0);
+    LlmPlan p;
+    KeepRows k{};
+    plan_llm(*c, R, true, a, p);
+    plan_keep(*c, n_keep, a, k);
+    return al256(a.off);
+}
+
+extern "C" int devqa_llm_prefix_rows(devqa_ctx_t h, float* x, const int32_t* positions, const int32_t* seq_desc, int n_seq, int max_len, int R, int dense,
+                                     int first_layer, int n_layers, const int32_t* keep_rows_host, const int32_t* keep_rows, int n_keep,
+                                     void* out_fc2_in, float* out_resid, void* workspace, int64_t ws_bytes, void* stream) {
+    CTX_OR_FAIL(h);
+    DEVQA_CHECK_ARG(x && seq_desc && workspace && out_fc2_in && out_resid, "llm_prefix_rows: null pointer");
+    DEVQA_CHECK_ARG(keep_rows_host && keep_rows, "llm_prefix_rows: needs the kept rows in host and in device memory");
+    DEVQA_CHECK_ARG(!llama_dec(c) || positions, "llm_prefix_rows: the LLaMA decoder needs the rotary positions of the rows");
+    if (R == 0 || n_seq == 0 || n_keep == 0) return DEVQA_OK;
+    if (n_layers < 0) n_layers = c.d.t_layers - first_layer;
+    DEVQA_CHECK_SHAPE(R > 0 && n_seq > 0 && max_len > 0 && first_layer >= 0 && n_layers >= 1 && first_layer + n_layers <= c.d.t_layers,
+                      "llm_prefix_rows: bad dims R=%d n_seq=%d first=%d layers=%d", R, n_seq, first_layer, n_layers);
+    DEVQA_CHECK_ARG(n_keep > 0 && n_keep <= R, "llm_prefix_rows: n_keep=%d of R=%d rows", n_keep, R);
+    for (int i = 0; i < n_keep; ++i) {      // checked on the host copy, before anything is launched
+        const int32_t r = keep_rows_host[i];
+        DEVQA_CHECK_ARG(r >= 0 && r < R, "llm_prefix_rows: keep_rows[%d] = %d is outside [0, %d)", i, (int)r, R);
+        DEVQA_CHECK_ARG(i == 0 || r > keep_rows_host[i - 1], "llm_prefix_rows: keep_rows must be sorted and unique (entry %d)", i);
+    }
+    DEVQA_CHECK_ARG((((uintptr_t)workspace) & 255) == 0, "llm_prefix_rows: workspace must be 256-byte aligned");
+    Arena a(workspace, ws_bytes);
+    LlmPlan w;
+    KeepRows k{};
+    plan_llm(c, R, true, a, w);
+    plan_keep(c, n_keep, a, k);
+    if (a.overflow) return devqa_fail(DEVQA_E_SHAPE, "llm_prefix_rows: workspace of %lld bytes is too small (need %lld)", (long long)ws_bytes, (long long)al256(a.off));
+    k.idx = keep_rows; k.n = n_keep; k.resid = out_resid;
+    return llm_layers(c, x, positions, seq_desc, n_seq, max_len, R, dense, first_layer, n_layers, 1, out_fc2_in, w, (hipStream_t)stream, &k);
 }
 
 // SURVEY.md 8(b)'s name for the frozen prefix of FT_VL: all layers, the last one stopping at its fc2 input

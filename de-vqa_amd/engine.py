@@ -520,8 +520,11 @@ class Blip2Engine:
     # stop_before_fc2, the last processed layer stops at the fc2 input: returns (x_mid, a_bf16).
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def decoder_layers(self, ps: PackedSeqs, upto_layer=None, stop_before_fc2=False, save=None, return_h=False, first_layer=0):
-        """save: None, or {"layers": set of layer ids}; filled with save[i] = activations the backward of layer i needs
+    def decoder_layers(self, ps: PackedSeqs, upto_layer=None, stop_before_fc2=False, save=None, return_h=False, first_layer=0, keep_rows=None):
+        """keep_rows (with stop_before_fc2): sorted, unique row numbers; returns (x_mid[keep_rows], a[keep_rows]) -- the path context
+        then runs the last layer behind its attention on these rows alone (devqa_llm_prefix_rows, same bits), and ps.x is left
+        holding the residual stream before that layer.
+        save: None, or {"layers": set of layer ids}; filled with save[i] = activations the backward of layer i needs
         (decoder_backward).  Low-rank module deltas registered in self.module_deltas (MEND_VL's forward_edit_hook,
         mend_vl.py:73-80) are applied to the fc1 / fc2 outputs."""
         t = self.t
@@ -531,6 +534,13 @@ class Blip2Engine:
         n_seq = ps.desc.shape[0]
         last = t["num_hidden_layers"] - 1 if upto_layer is None else upto_layer
         ctx = self.path_ctx() if (save is None and not return_h and first_layer == 0 and not self._hooks_active()) else None
+        if keep_rows is not None:
+            assert stop_before_fc2 and not return_h and save is None
+            if ctx is not None:
+                return ctx.llm_prefix_rows(x, ps.desc, n_seq, ps.max_len, ps.dense, keep_rows, last + 1)
+            x, a = self.decoder_layers(ps, upto_layer, True, first_layer=first_layer)     # the cross-check schedule: all rows, then the gather
+            kd = lib.h2d(list(keep_rows), torch.int32, self.dev)
+            return lib.gather_rows(x, kd), lib.gather_rows(a, kd)
         if ctx is not None:
             a = ctx.llm_layers(x, ps.desc, n_seq, ps.max_len, ps.dense, last + 1, stop_before_fc2)
             return x, a

@@ -235,8 +235,11 @@ class LlavaEngine:
 
     # ---- LLaMA decoder layers -----------------------------------------------------------------------------------
     @torch.no_grad()
-    def decoder_layers(self, ps, upto_layer=None, stop_before_fc2=False, save=None, return_h=False, first_layer=0):
-        """save: None, or {"layers": set of layer ids}: filled with the activations decoder_backward needs.  Low-rank module
+    def decoder_layers(self, ps, upto_layer=None, stop_before_fc2=False, save=None, return_h=False, first_layer=0, keep_rows=None):
+        """keep_rows (with stop_before_fc2): sorted, unique row numbers; returns (x_mid[keep_rows], a[keep_rows]) -- the path context
+        then runs the last layer behind its attention on these rows alone (devqa_llm_prefix_rows, same bits), and ps.x is left
+        holding the residual stream before that layer.
+        save: None, or {"layers": set of layer ids}: filled with the activations decoder_backward needs.  Low-rank module
         deltas (set_module_deltas; MEND_VL's forward_edit_hook, mend_vl.py:73-80) are applied to gate / up / down outputs."""
         t, m = self.t, self.m
         d, H = t["hidden_size"], t["num_attention_heads"]
@@ -246,6 +249,14 @@ class LlavaEngine:
         last = t["num_hidden_layers"] - 1 if upto_layer is None else upto_layer
         deltas = getattr(self, "module_deltas", None) or {}
         ctx = self.path_ctx() if (save is None and not return_h and not self._hooks_active() and last >= first_layer) else None
+        if keep_rows is not None:
+            assert stop_before_fc2 and not return_h and save is None
+            if ctx is not None:
+                return ctx.llm_prefix_rows(x, ps.desc, n_seq, ps.max_len, getattr(ps, "dense", False), keep_rows, last + 1 - first_layer,
+                                           positions=ps.pos, first_layer=first_layer)
+            x, a = self.decoder_layers(ps, upto_layer, True, first_layer=first_layer)     # the cross-check schedule: all rows, then the gather
+            kd = lib.h2d(list(keep_rows), torch.int32, self.dev)
+            return lib.gather_rows(x, kd), lib.gather_rows(a, kd)
         if ctx is not None:     # plain frozen layers: one path-level call (devqa_llm_layers_ex) instead of ~10 Python-ordered launches per layer
             a = ctx.llm_layers(x, ps.desc, n_seq, ps.max_len, getattr(ps, "dense", False), last + 1 - first_layer, stop_before_fc2,
                                positions=ps.pos, first_layer=first_layer)

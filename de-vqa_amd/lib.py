@@ -7,6 +7,7 @@ import ctypes
 import os
 from ctypes import c_float, c_int, c_int64, c_void_p
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -78,6 +79,11 @@ def load():
     _sig(L.devqa_gather_cols_f32, [P, I64, I64, I, P, I64, P, I, I, P, P])
     _sig(L.devqa_gather_cols_bf16, [P, I64, I64, I, P, I64, P, I, I, P, P])
     _sig(L.devqa_scatter_cols_add_f32, [P, I, P, P, I, P, I64, P])
+    _sig(L.devqa_gather_cols_grouped_f32, [P, I64, I, P, P, I64, P, I, I, P, P])
+    _sig(L.devqa_gather_cols_grouped_bf16, [P, I64, I, P, P, I64, P, I, I, P, P])
+    _sig(L.devqa_gemm_grouped_supported, [I, I])
+    _sig(L.devqa_gemm_grouped_bf16, [P, I64, P, I64, I64, P, I, I, I, I, I, I, P, I64, P])
+    _sig(L.devqa_gemm_grouped_f32, [P, I64, P, I64, I64, P, I, I, I, I, I, I, P, I64, P])
     _sig(L.devqa_rows_matvec_f32, [P, I64, P, P, P, P, I, I, I, I, P])
     _sig(L.devqa_delta_op, [I, P, P, P, I64, P])
     _sig(L.devqa_ft_step_control, [P, P, I, I, I, I, F, P, P, P, P, P, P])
@@ -117,6 +123,8 @@ def load():
     _sig(L.devqa_llm_layers_ex, [U64, P, P, P, I, I, I, I, I, I, I, P, P, I64, P])
     _sig(L.devqa_llm_prefix_workspace, [U64, I], c_int64)
     _sig(L.devqa_llm_prefix, [U64, P, P, I, I, I, I, P, P, I64, P])
+    _sig(L.devqa_llm_prefix_rows_workspace, [U64, I, I], c_int64)
+    _sig(L.devqa_llm_prefix_rows, [U64, P, P, P, I, I, I, I, I, I, P, P, I, P, P, P, I64, P])
     _sig(L.devqa_mend_transform_workspace, [I, I, I, I], c_int64)
     _sig(L.devqa_mend_transform, [P, P, P, I, I, I, P, P, P, P, I64, P])
     _sig(L.devqa_mend_apply_workspace, [I, I, I], c_int64)
@@ -141,12 +149,14 @@ def load():
 
 
 EXPORTS = ["devqa_ctx_create", "devqa_ctx_destroy", "devqa_ctx_set_weight", "devqa_vision_encode_workspace", "devqa_vision_encode",
-           "devqa_llm_layers_workspace", "devqa_llm_layers", "devqa_llm_layers_ex", "devqa_llm_forward_ex", "devqa_llm_prefix_workspace", "devqa_llm_prefix", "devqa_mend_transform_workspace",
+           "devqa_llm_layers_workspace", "devqa_llm_layers", "devqa_llm_layers_ex", "devqa_llm_forward_ex", "devqa_llm_prefix_workspace", "devqa_llm_prefix",
+           "devqa_llm_prefix_rows_workspace", "devqa_llm_prefix_rows", "devqa_mend_transform_workspace",
            "devqa_mend_transform", "devqa_mend_apply_workspace", "devqa_mend_apply", "devqa_llm_head_workspace", "devqa_llm_head", "devqa_llm_forward_workspace",
            "devqa_llm_forward", "devqa_ft_edit_workspace", "devqa_ft_edit", "devqa_ctx_bind_edit_target", "devqa_apply_delta", "devqa_restore",
            "devqa_token_acc", "devqa_comm_unique_id", "devqa_comm_create", "devqa_comm_destroy", "devqa_gather_scores",
            "devqa_profile", "devqa_profile_read", "devqa_profile_dropped", "devqa_attention_reload_env", "devqa_act_cast", "devqa_row_inv_norm", "devqa_cosine_topk_cached", "devqa_rmsnorm", "devqa_rmsnorm_bwd_dx", "devqa_rope_bf16", "devqa_rope_f32", "devqa_swiglu_bf16", "devqa_swiglu_f32",
            "devqa_gemm_bf16_splitk", "devqa_gemm_set_mode", "devqa_active_columns", "devqa_gather_cols_f32", "devqa_gather_cols_bf16", "devqa_scatter_cols_add_f32",
+           "devqa_gather_cols_grouped_f32", "devqa_gather_cols_grouped_bf16", "devqa_gemm_grouped_supported", "devqa_gemm_grouped_bf16", "devqa_gemm_grouped_f32",
            "devqa_profile_gemm", "devqa_profile_gemm_read", "devqa_last_error", "devqa_abi_version", "devqa_gemm_bf16", "devqa_gemm_f32", "devqa_attention_f32",
            "devqa_im2col_patches_f32", "devqa_embed_rows_f32", "devqa_vocab_rows_f32", "devqa_layernorm", "devqa_attention",
            "devqa_im2col_patches", "devqa_vit_assemble", "devqa_embed_rows", "devqa_gather_rows", "devqa_cast_f32_bf16", "devqa_split_f32_bf16x2", "devqa_gemm_bf16_swiglu_supported",
@@ -613,6 +623,50 @@ def gather_cols(src, idx, count, npad, per_edit):
     return out
 
 
+class TailSegments:
+    """Host-built tables of the grouped post-edit tail for row segments [(r0, r1)] (segment e belongs to edit e): row_edit int32 [R] and
+    the row-tile table int32 [n_tiles, 3] = (edit, first row, end row of the segment), on `device` through pinned non-blocking copies."""
+
+    def __init__(self, segments, dtype, device):
+        rows_max = max([r1 - r0 for r0, r1 in segments] + [0])
+        self.bm = 64 if (dtype == torch.float32 or rows_max > 32) else 32         # the row tile a per-edit GEMM call takes
+        self.E = len(segments)
+        self.R = max([r1 for _, r1 in segments] + [0])
+        row_edit = np.full((self.R,), -1, np.int32)
+        tab = []
+        for e, (r0, r1) in enumerate(segments):
+            row_edit[r0:r1] = e
+            tab += [(e, m0, r1) for m0 in range(r0, r1, self.bm)]
+        self.n_tiles = len(tab)
+        self.row_edit = h2d(torch.from_numpy(row_edit), torch.int32, device)
+        self.tab = h2d(torch.from_numpy(np.asarray(tab, np.int32).reshape(-1, 3)), torch.int32, device)
+
+
+def gemm_grouped_supported(dtype, K):
+    """the grouped tail's K order equals one gemm call per edit (no split-K there) for this reduction length"""
+    return bool(load().devqa_gemm_grouped_supported(DTYPE_F32 if dtype == torch.float32 else DTYPE_BF16, int(K)))
+
+
+def tail_grouped_(a_tail, seg, idx, cnt, npad, delta_op, y):
+    """y[r0:r1] += gather_cols(a_tail[r0:r1], idx[e], cnt[e], npad) @ delta_op[e].T for every segment e of `seg` (TailSegments), in place:
+    one grouped gather and one grouped GEMM (devqa_gather_cols_grouped_*, devqa_gemm_grouped_*) instead of two launches per edit."""
+    assert a_tail.is_contiguous() and a_tail.dim() == 2 and a_tail.shape[0] >= seg.R and delta_op.dtype == a_tail.dtype
+    assert idx.dtype == torch.int32 and cnt.dtype == torch.int32 and idx.shape[0] == seg.E and delta_op.is_contiguous()
+    E, N, K = delta_op.shape
+    assert E == seg.E and K == npad
+    _need(y, torch.float32, "tail_grouped y")
+    assert y.shape == (a_tail.shape[0], N)
+    f32 = a_tail.dtype == torch.float32
+    a_pc = torch.empty((seg.R, npad), dtype=a_tail.dtype, device=a_tail.device)
+    L = load()
+    _chk((L.devqa_gather_cols_grouped_f32 if f32 else L.devqa_gather_cols_grouped_bf16)(
+        _p(a_tail), a_tail.shape[1], seg.R, _p(seg.row_edit), _p(idx), idx.stride(0), _p(cnt), E, int(npad), _p(a_pc), _stream()),
+        "devqa_gather_cols_grouped")
+    _chk((L.devqa_gemm_grouped_f32 if f32 else L.devqa_gemm_grouped_bf16)(
+        _p(a_pc), npad, _p(delta_op), K, N * K, _p(seg.tab), seg.n_tiles, seg.bm, E, seg.R, N, K, _p(y), N, _stream()), "devqa_gemm_grouped")
+    return y
+
+
 def scatter_cols_add(comp, idx_e, count_e, dense):
     """dense[:, idx_e[c]] += comp[:, c] for c < count_e (one edit)."""
     rows, npad = comp.shape
@@ -1020,6 +1074,29 @@ class PathContext:
         _chk(load().devqa_llm_layers_ex(self.h, _p(x), _p(positions), _p(seq_desc), int(n_seq), int(max_len), R, int(bool(dense)), int(first_layer),
                                         int(n_layers), int(bool(stop_before_fc2)), _p(a), ws, n, _stream()), "devqa_llm_layers_ex")
         return a
+
+    def llm_prefix_rows(self, x, seq_desc, n_seq, max_len, dense, keep_rows, n_layers=-1, positions=None, first_layer=0):
+        """devqa_llm_prefix_rows: layers [first_layer, first_layer + n_layers), the last one stopping at its fc2 input and running
+        everything behind its attention on the rows `keep_rows` alone (sorted, unique host ints).  -> (resid fp32 [n_keep, d],
+        fc2 / down_proj input [n_keep, ffn]): the kept rows of the all-rows call's (x, a), bit for bit.  x is left holding the residual
+        stream BEFORE the last layer."""
+        _need(x, torch.float32, "llm_prefix_rows x")
+        R = x.shape[0]
+        if positions is not None:
+            assert positions.dtype == torch.int32 and positions.is_cuda and positions.is_contiguous() and positions.numel() == R
+        kh = np.ascontiguousarray(np.asarray(keep_rows, dtype=np.int32).reshape(-1))
+        nk = int(kh.size)
+        kd = h2d(torch.from_numpy(kh), torch.int32, x.device)
+        a = torch.empty((nk, self.desc.t_ffn), dtype=self.adt, device=x.device)
+        resid = torch.empty((nk, self.desc.t_hidden), dtype=torch.float32, device=x.device)
+        if nk == 0:
+            raise DevqaError("llm_prefix_rows: empty keep_rows")
+        n = load().devqa_llm_prefix_rows_workspace(self.h, R, min(nk, R))
+        keep, ws = _ws(n, x.device)
+        _chk(load().devqa_llm_prefix_rows(self.h, _p(x), _p(positions), _p(seq_desc), int(n_seq), int(max_len), R, int(bool(dense)), int(first_layer),
+                                          int(n_layers), c_void_p(kh.ctypes.data), _p(kd), nk, _p(a), _p(resid), ws, n, _stream()),
+             "devqa_llm_prefix_rows")
+        return resid, a
 
     def llm_prefix(self, x, seq_desc, n_seq, max_len, dense):
         """SURVEY 8(b)'s devqa_llm_prefix: all layers in place on x, the last one stopping at its fc2 input -> [R, ffn]"""

@@ -370,6 +370,26 @@ int devqa_gather_cols_bf16(const devqa_bf16* src, int64_t src_stride_e, int64_t 
 int devqa_scatter_cols_add_f32(const float* comp, int rows, const int32_t* idx, const int32_t* count, int npad, float* dense,
                                int64_t ld_dense, void* stream);
 
+/* ---- grouped post-edit tail: y_post[rows of cycle e] += a_tail[rows of cycle e][:, J_e] . delta_e^T for ALL cycles in two launches
+ * (one gather, one GEMM) instead of two per cycle.
+ *   devqa_gather_cols_grouped_* : out[r, c] = c < count[row_edit[r]] ? src[r*ld_src + idx[row_edit[r]*idx_stride_e + c]] : 0 for the
+ *                                 `rows` rows of ONE matrix, row_edit int32 [rows] = the edit a row belongs to.
+ *   devqa_gemm_grouped_*        : y[m, :] += A[m, :K] . W[e]^T (W: E matrices [N, K], w_stride_e elements apart; y fp32, ldc) for the row
+ *                                 tiles listed in tile_tab int32 [n_tiles][3] = (edit e, first row, END row of e's segment): a tile covers
+ *                                 rows [first, min(first + bm, end)); bm = 32 or 64 (bf16), 64 (fp32).  Entries outside [0, E) x [0, R] are
+ *                                 skipped.  The tile code and K order of one devqa_gemm_bf16 / devqa_gemm_f32 call per edit, hence the
+ *                                 same bits -- for K below those calls' split-K rules, which devqa_gemm_grouped_supported(dtype, K)
+ *                                 tells (otherwise DEVQA_E_SHAPE: loop over the edits). */
+int devqa_gather_cols_grouped_f32(const float* src, int64_t ld_src, int rows, const int32_t* row_edit, const int32_t* idx, int64_t idx_stride_e,
+                                  const int32_t* count, int E, int npad, float* out, void* stream);
+int devqa_gather_cols_grouped_bf16(const devqa_bf16* src, int64_t ld_src, int rows, const int32_t* row_edit, const int32_t* idx,
+                                   int64_t idx_stride_e, const int32_t* count, int E, int npad, devqa_bf16* out, void* stream);
+int devqa_gemm_grouped_supported(int dtype, int K);
+int devqa_gemm_grouped_bf16(const devqa_bf16* A, int64_t lda, const devqa_bf16* W, int64_t ldw, int64_t w_stride_e, const int32_t* tile_tab,
+                            int n_tiles, int bm, int E, int R, int N, int K, float* y, int64_t ldc, void* stream);
+int devqa_gemm_grouped_f32(const float* A, int64_t lda, const float* W, int64_t ldw, int64_t w_stride_e, const int32_t* tile_tab, int n_tiles,
+                           int bm, int E, int R, int N, int K, float* y, int64_t ldc, void* stream);
+
 /* y[e,r,:] = W[e or shared] . a[e,r,:] (+ bias) (+ resid[e,r,:]) : fc2 on a few cached rows with an
  * fp32 matrix (pre-/post-edit probe tails, step-0 forward).  w_stride_e = 0 shares one matrix.  1 <= L <= DEVQA_FT_MAX_ROWS. */
 int devqa_rows_matvec_f32(const float* w, int64_t w_stride_e, const float* a, const float* bias, const float* resid,
@@ -514,6 +534,20 @@ int devqa_llm_layers_ex(devqa_ctx_t ctx, float* x, const int32_t* positions, con
 int64_t devqa_llm_prefix_workspace(devqa_ctx_t ctx, int R);
 int devqa_llm_prefix(devqa_ctx_t ctx, float* x, const int32_t* seq_desc, int n_seq, int max_len, int R, int dense, void* out_fc2_in,
                      void* workspace, int64_t ws_bytes, void* stream);
+/* The frozen prefix for a caller that reads only SOME rows of it (batched FT_VL: the label rows of the probes and the loss rows of the
+ * edits, ~6 % of a packed batch): devqa_llm_layers_ex(..., stop_before_fc2 = 1) whose LAST layer runs its norm, fused q|k|v GEMM and
+ * attention on all R rows (other rows attend to their keys and values) and everything behind the attention -- out_proj + residual, the
+ * second norm, fc1 + activation (LLaMA: gate|up + SwiGLU, fused or not) -- on the n_keep listed rows alone.
+ *   keep_rows_host / keep_rows : the same int32 [n_keep] list in host and in device memory: sorted, unique, each in [0, R).  The host
+ *                                copy is validated before anything is launched (DEVQA_E_ARG); the device copy feeds the kernels.
+ *   out_fc2_in [n_keep, t_ffn] (compute dtype), out_resid fp32 [n_keep, t_hidden]: the kept rows of out_fc2_in and of x as the
+ *                                all-rows call leaves them, BIT FOR BIT in both compute modes (the GEMMs take the kernel family and
+ *                                the split-K slicing of the R-row call).
+ * On return x holds the residual stream BEFORE the last layer (after layer first_layer + n_layers - 2), not the all-rows call's x. */
+int64_t devqa_llm_prefix_rows_workspace(devqa_ctx_t ctx, int R, int n_keep);
+int devqa_llm_prefix_rows(devqa_ctx_t ctx, float* x, const int32_t* positions, const int32_t* seq_desc, int n_seq, int max_len, int R, int dense,
+                          int first_layer, int n_layers, const int32_t* keep_rows_host, const int32_t* keep_rows, int n_keep, void* out_fc2_in,
+                          float* out_resid, void* workspace, int64_t ws_bytes, void* stream);
 /* K8: logits fp32 [R, t_vocab] = lm_head(final LayerNorm(rows [+ add])), rows / add fp32 [R, t_hidden] (tied embedding, no bias) */
 int64_t devqa_llm_head_workspace(devqa_ctx_t ctx, int R);
 int devqa_llm_head(devqa_ctx_t ctx, const float* rows, const float* add, int R, float* out_logits, void* workspace, int64_t ws_bytes,
