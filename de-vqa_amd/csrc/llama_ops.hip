@@ -2,6 +2,7 @@
 // RMSNorm forward / backward-dx, rotary position embedding, SwiGLU gate.  HBM-bound: 16-byte accesses,
 // one wave per row for the reductions (wavefront shuffles, row held in registers).
 #include "common.h"
+#include <cmath>
 #include <type_traits>
 
 #define RN_MAXV 16
@@ -129,11 +130,29 @@ __device__ __forceinline__ float ldf(const float* p) { return *p; }
 __device__ __forceinline__ void stf(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 __device__ __forceinline__ void stf(float* p, float v) { *p = v; }
 
+// inv_freq[j] = theta^(-2j/dh), j < dh/2 <= 64: computed on the host in double and rounded ONCE (within half an ulp, as good as HF's fp32
+// table), passed by value; the lanes no longer evaluate exp2f(-log2f(theta) * 2j/dh).  At position 2047 one ulp of inv_freq[1] is 1e-4 rad
+// of angle, as much as the fp32 angle's own rounding, so that chain met the 2x-of-HF bar of tests/test_llama_ops_gpu.py::test_rope_f32 only
+// as far as the device exp2f happened to round correctly (docstring there).
+struct RopeFreq { float v[64]; };
+
+static const RopeFreq& rope_freq(float theta, int dh) {          // the last (theta, dh) of this thread: one model, one table
+    static thread_local RopeFreq f;
+    static thread_local float f_theta = 0.f;
+    static thread_local int f_dh = 0;
+    if (f_theta != theta || f_dh != dh) {
+        for (int j = 0; j < 64; ++j) f.v[j] = j < dh / 2 ? (float)pow((double)theta, -2.0 * j / dh) : 0.f;
+        f_theta = theta;
+        f_dh = dh;
+    }
+    return f;
+}
+
 // One wave per row: lane -> (head slot = lane / half, j = lane % half); the angle depends on (pos[row], j) only, so sin / cos
 // are computed ONCE per row and lane (full-precision sincosf) and reused for every head the lane visits.
 template <typename T>
 __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ x, int64_t ld, int R, const int32_t* __restrict__ pos, int n_heads,
-                                                   int dh, float log2_theta) {
+                                                   int dh, const RopeFreq freq) {
     const int half = dh >> 1;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -141,9 +160,8 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ x, int64_t ld
     const int hp = half >= 64 ? 1 : 64 / half;          // heads per pass (half <= 64: checked on the host)
     const int slot = lane / half, j = lane - slot * half;
     if (slot >= hp) return;
-    const float inv_freq = exp2f(-log2_theta * (2.0f * (float)j / (float)dh));
     float sn, cs;
-    sincosf((float)pos[row] * inv_freq, &sn, &cs);
+    sincosf((float)pos[row] * freq.v[j], &sn, &cs);
     T* base = x + (int64_t)row * ld + j;
     for (int h = slot; h < n_heads; h += hp) {
         T* p = base + (int64_t)h * dh;
@@ -159,7 +177,7 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ x, int64_t ld
 // rotation is the same two fp32 expressions per element: bit-identical.  Two passes are loaded before the first store (a load behind a
 // pending store costs the compiler a vmcnt(0) on gfx950).
 __global__ __launch_bounds__(256) void rope_bf16x8_kernel(bf16_t* __restrict__ x, int64_t ld, int R, const int32_t* __restrict__ pos, int n_heads,
-                                                          int dh, float log2_theta) {
+                                                          int dh, const RopeFreq freq) {
     const int half = dh >> 1, lph = half >> 3;            // lanes per head
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -170,10 +188,7 @@ __global__ __launch_bounds__(256) void rope_bf16x8_kernel(bf16_t* __restrict__ x
     float sn[8], cs[8];
     const float p_ = (float)pos[row];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const float inv_freq = exp2f(-log2_theta * (2.0f * (float)(j0 + u) / (float)dh));
-        sincosf(p_ * inv_freq, &sn[u], &cs[u]);
-    }
+    for (int u = 0; u < 8; ++u) sincosf(p_ * freq.v[j0 + u], &sn[u], &cs[u]);
     bf16_t* base = x + (int64_t)row * ld + j0;
     auto rot = [&](const uint4& a4, const uint4& b4, uint4& oa, uint4& ob) {
         const uint32_t aw[4] = {a4.x, a4.y, a4.z, a4.w}, bw[4] = {b4.x, b4.y, b4.z, b4.w};
@@ -221,14 +236,15 @@ static int launch_rope(T* x, int64_t ld, int R, const int32_t* pos, int n_heads,
     if (R == 0) return DEVQA_OK;
     DEVQA_CHECK_SHAPE(R > 0 && n_heads > 0 && dh > 0 && dh % 2 == 0 && dh <= 128 && ld >= (int64_t)n_heads * dh && theta > 1.f,
                       "rope: bad dims (dh even, <= 128)");
+    const RopeFreq freq = rope_freq(theta, dh);
     if constexpr (std::is_same<T, bf16_t>::value) {
         if ((dh & 31) == 0 && 64 % (dh >> 4) == 0 && (ld & 7) == 0 && (((uintptr_t)x) & 15) == 0) {       // half % 16 == 0: 16-byte pieces stay 16-byte aligned
-            hipLaunchKernelGGL(rope_bf16x8_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, ld, R, pos, n_heads, dh, log2f(theta));
+            hipLaunchKernelGGL(rope_bf16x8_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, ld, R, pos, n_heads, dh, freq);
             DEVQA_LAUNCH_CHECK("rope");
             return DEVQA_OK;
         }
     }
-    hipLaunchKernelGGL(rope_kernel<T>, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ld, R, pos, n_heads, dh, log2f(theta));
+    hipLaunchKernelGGL(rope_kernel<T>, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ld, R, pos, n_heads, dh, freq);
     DEVQA_LAUNCH_CHECK("rope");
     return DEVQA_OK;
 }

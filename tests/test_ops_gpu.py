@@ -1,6 +1,8 @@
-"""Op-level parity of every C-ABI entry point against plain fp32 PyTorch (CPU) on the same
-(bf16-rounded) inputs.  Integer outputs (argmax, top-k ids) must match exactly; floating point
-tolerances are written per test."""
+"""Op-level parity of C-ABI entry points against plain PyTorch on the CPU, on the same (bf16-rounded) inputs: the GEMMs, LayerNorm, both
+attention forwards and the backward, the vision / embedding / vocabulary row ops, the FT_VL step, retrieval top-k and column compaction.
+The LLaMA row ops are in tests/test_llama_ops_gpu.py, the MEND / LTE training row ops in tests/test_mend_train_ops_gpu.py, the T-Patcher
+neuron ops in tests/test_tp_neuron_ops_gpu.py; tests/test_op_coverage_cpu.py names the test that holds each exported symbol.
+Integer outputs (argmax, top-k ids) must match exactly; floating point tolerances are written per test."""
 import numpy as np
 import pytest
 import torch
@@ -92,8 +94,9 @@ def test_layernorm_fwd_bwd(L, M, D, eps):
     np.testing.assert_allclose(dx.cpu().numpy(), xr.grad.numpy(), atol=2e-5, rtol=1e-4)
 
 
-def _ref_attention(q, k, v, desc, H, dh, scale, causal):
-    out = torch.zeros(q.shape[0], H * dh)
+def _ref_attention(q, k, v, desc, H, dh, scale, causal, dtype=torch.float32):
+    q, k, v = q.to(dtype), k.to(dtype), v.to(dtype)
+    out = torch.zeros(q.shape[0], H * dh, dtype=dtype)
     for (qs, ql, kps, kpl, kos, kol) in desc:
         for h in range(H):
             qq = q[qs:qs + ql, h * dh:(h + 1) * dh]
@@ -109,59 +112,57 @@ def _ref_attention(q, k, v, desc, H, dh, scale, causal):
     return out
 
 
-@pytest.mark.parametrize("name", ["vit", "qformer_cross", "opt_causal", "opt_prefix", "opt_pack_short", "llama_pack_short", "tiny_heads",
-                                  "clip_l_577", "llama_dh128", "llama_prefix_576", "opt_pack_32", "llama_pack_32", "dh64_pack_32"])
-def test_attention(L, name):
-    g = torch.Generator().manual_seed(11)
+def _attention_case(name, g, rnd):
+    """q, k, v (fp32 on the CPU, `rnd` applied to the random values: bf for the bf16 kernels, nothing for fp32), descriptors and the rows that
+    carry output of one named case; "vit" packs q | k | v in ONE fused buffer (returned too: the kernels then see strided views)"""
+    qkv = n = None
     keep = slice(None)
     if name == "vit":  # 2 images x 257 tokens, fused qkv buffer
         H, dh, n = 16, 88, 257
-        qkv = bf(torch.randn(2 * n, 3 * H * dh, generator=g))
+        qkv = rnd(torch.randn(2 * n, 3 * H * dh, generator=g))
         q, k, v = qkv[:, :H * dh], qkv[:, H * dh:2 * H * dh], qkv[:, 2 * H * dh:]
         desc = [(0, n, 0, n, 0, 0), (n, n, n, n, 0, 0)]
         causal, scale = 0, dh ** -0.5
-        dq = dev(qkv).to(torch.bfloat16)
-        views = (dq[:, :H * dh], dq[:, H * dh:2 * H * dh], dq[:, 2 * H * dh:])
     else:
         if name == "qformer_cross":
             H, dh = 12, 64
-            q = bf(torch.randn(64, H * dh, generator=g))
-            k = bf(torch.randn(514, H * dh, generator=g))
-            v = bf(torch.randn(514, H * dh, generator=g))
+            q = rnd(torch.randn(64, H * dh, generator=g))
+            k = rnd(torch.randn(514, H * dh, generator=g))
+            v = rnd(torch.randn(514, H * dh, generator=g))
             desc = [(0, 32, 0, 257, 0, 0), (32, 32, 257, 257, 0, 0)]
             causal, scale = 0, dh ** -0.5
         elif name == "opt_causal":
             H, dh = 32, 80
             T = [48, 17, 70]
             tot = sum(T)
-            q = bf(torch.randn(tot, H * dh, generator=g))
-            k = bf(torch.randn(tot, H * dh, generator=g))
-            v = bf(torch.randn(tot, H * dh, generator=g))
+            q = rnd(torch.randn(tot, H * dh, generator=g))
+            k = rnd(torch.randn(tot, H * dh, generator=g))
+            v = rnd(torch.randn(tot, H * dh, generator=g))
             st = np.cumsum([0] + T)
             desc = [(int(st[i]), T[i], 0, 0, int(st[i]), T[i]) for i in range(3)]
             causal, scale = 1, 1.0
         elif name == "clip_l_577":   # CLIP ViT-L/14-336 of LLaVA-1.5: 576 patches + CLS, 16 heads x 64, own-range descriptors
             H, dh, n = 16, 64, 577
-            q = bf(torch.randn(2 * n, H * dh, generator=g))
-            k = bf(torch.randn(2 * n, H * dh, generator=g))
-            v = bf(torch.randn(2 * n, H * dh, generator=g))
+            q = rnd(torch.randn(2 * n, H * dh, generator=g))
+            k = rnd(torch.randn(2 * n, H * dh, generator=g))
+            v = rnd(torch.randn(2 * n, H * dh, generator=g))
             desc = [(0, n, 0, 0, 0, n), (n, n, 0, 0, n, n)]
             causal, scale = 0, dh ** -0.5
         elif name == "llama_dh128":  # Vicuna-7B heads (32 x 128), causal, ~600-token sequences (576 image tokens + text)
             H, dh = 32, 128
             T = [598, 46, 130]
             tot = sum(T)
-            q = bf(torch.randn(tot, H * dh, generator=g))
-            k = bf(torch.randn(tot, H * dh, generator=g))
-            v = bf(torch.randn(tot, H * dh, generator=g))
+            q = rnd(torch.randn(tot, H * dh, generator=g))
+            k = rnd(torch.randn(tot, H * dh, generator=g))
+            v = rnd(torch.randn(tot, H * dh, generator=g))
             st = np.cumsum([0] + T)
             desc = [(int(st[i]), T[i], 0, 0, int(st[i]), T[i]) for i in range(3)]
             causal, scale = 1, dh ** -0.5
         elif name == "llama_prefix_576":  # a shared 576-row image prefix (9 chunks) + two texts attending to it, head dim 128
             H, dh = 8, 128
-            q = bf(torch.randn(576 + 20 + 70, H * dh, generator=g))
-            k = bf(torch.randn(576 + 20 + 70, H * dh, generator=g))
-            v = bf(torch.randn(576 + 20 + 70, H * dh, generator=g))
+            q = rnd(torch.randn(576 + 20 + 70, H * dh, generator=g))
+            k = rnd(torch.randn(576 + 20 + 70, H * dh, generator=g))
+            v = rnd(torch.randn(576 + 20 + 70, H * dh, generator=g))
             desc = [(0, 576, 0, 0, 0, 576), (576, 20, 0, 576, 576, 20), (596, 70, 0, 576, 596, 70)]
             causal, scale = 1, dh ** -0.5
         elif name in ("opt_pack_32", "llama_pack_32", "dh64_pack_32"):
@@ -172,9 +173,9 @@ def test_attention(L, name):
             pre = [None, 0, 0, 0, None, 4, 4, 4, None, None, None, 10]
             st = np.cumsum([0] + lens)
             tot = int(st[-1])
-            q = bf(torch.randn(tot, H * dh, generator=g))
-            k = bf(torch.randn(tot, H * dh, generator=g))
-            v = bf(torch.randn(tot, H * dh, generator=g))
+            q = rnd(torch.randn(tot, H * dh, generator=g))
+            k = rnd(torch.randn(tot, H * dh, generator=g))
+            v = rnd(torch.randn(tot, H * dh, generator=g))
             desc = [(int(st[i]), lens[i], int(st[pre[i]]) if pre[i] is not None else 0, lens[pre[i]] if pre[i] is not None else 0,
                      int(st[i]), lens[i]) for i in range(len(lens))]
             desc[10] = (int(st[10]), 0, 0, 0, int(st[10]), 0)        # the 150 rows are only ever a prefix (no queries of their own: q_len 0)
@@ -189,26 +190,40 @@ def test_attention(L, name):
             pre = [None, 0, 0, 0, None, 4, 4, 4, None, None]      # index of the prefix sequence each one sees
             st = np.cumsum([0] + lens)
             tot = int(st[-1])
-            q = bf(torch.randn(tot, H * dh, generator=g))
-            k = bf(torch.randn(tot, H * dh, generator=g))
-            v = bf(torch.randn(tot, H * dh, generator=g))
+            q = rnd(torch.randn(tot, H * dh, generator=g))
+            k = rnd(torch.randn(tot, H * dh, generator=g))
+            v = rnd(torch.randn(tot, H * dh, generator=g))
             desc = [(int(st[i]), lens[i], int(st[pre[i]]) if pre[i] is not None else 0, lens[pre[i]] if pre[i] is not None else 0,
                      int(st[i]), lens[i]) for i in range(len(lens))]
             causal, scale = 1, (1.0 if dh == 80 else dh ** -0.5)
         elif name == "opt_prefix":  # prefix seq (32 rows) + two text seqs attending to it
             H, dh = 32, 80
-            q = bf(torch.randn(32 + 16 + 21, H * dh, generator=g))
-            k = bf(torch.randn(32 + 16 + 21, H * dh, generator=g))
-            v = bf(torch.randn(32 + 16 + 21, H * dh, generator=g))
+            q = rnd(torch.randn(32 + 16 + 21, H * dh, generator=g))
+            k = rnd(torch.randn(32 + 16 + 21, H * dh, generator=g))
+            v = rnd(torch.randn(32 + 16 + 21, H * dh, generator=g))
             desc = [(0, 32, 0, 0, 0, 32), (32, 16, 0, 32, 32, 16), (48, 21, 0, 32, 48, 21)]
             causal, scale = 1, 1.0
         else:
             H, dh = 5, 8
-            q = bf(torch.randn(29, H * dh, generator=g))
-            k = bf(torch.randn(29, H * dh, generator=g))
-            v = bf(torch.randn(29, H * dh, generator=g))
+            q = rnd(torch.randn(29, H * dh, generator=g))
+            k = rnd(torch.randn(29, H * dh, generator=g))
+            v = rnd(torch.randn(29, H * dh, generator=g))
             desc = [(0, 29, 0, 0, 0, 29)]
             causal, scale = 1, 0.7
+    return dict(q=q, k=k, v=v, qkv=qkv, n=n, desc=desc, H=H, dh=dh, scale=scale, causal=causal, keep=keep)
+
+
+@pytest.mark.parametrize("name", ["vit", "qformer_cross", "opt_causal", "opt_prefix", "opt_pack_short", "llama_pack_short", "tiny_heads",
+                                  "clip_l_577", "llama_dh128", "llama_prefix_576", "opt_pack_32", "llama_pack_32", "dh64_pack_32"])
+def test_attention(L, name):
+    g = torch.Generator().manual_seed(11)
+    c = _attention_case(name, g, bf)
+    q, k, v, desc, H, dh, scale, causal, keep = (c[x] for x in ("q", "k", "v", "desc", "H", "dh", "scale", "causal", "keep"))
+    if name == "vit":
+        n = c["n"]
+        dq = dev(c["qkv"]).to(torch.bfloat16)
+        views = (dq[:, :H * dh], dq[:, H * dh:2 * H * dh], dq[:, 2 * H * dh:])
+    else:
         views = tuple(dev(t).to(torch.bfloat16) for t in (q, k, v))
     ref = _ref_attention(q, k, v, desc, H, dh, scale, causal)
     d = torch.tensor(desc, dtype=torch.int32, device="cuda")
@@ -268,6 +283,30 @@ def test_attention(L, name):
         np.testing.assert_allclose(out2.float().cpu().numpy(), ref.numpy(), atol=2e-2, rtol=2e-2)
 
 
+@pytest.mark.parametrize("name", ["vit", "qformer_cross", "opt_causal", "opt_prefix", "opt_pack_short", "llama_pack_short", "tiny_heads",
+                                  "llama_prefix_576"])
+def test_attention_f32(L, name):
+    """devqa_attention_f32 (the VALU kernel of csrc/attention.hip: the forward attention of the whole fp32 compute mode) on the cases of
+    test_attention with UNROUNDED fp32 q / k / v, against float64: max |err| / max |ref| < 2e-5 over the rows that carry output (the fp32
+    bar of test_attention_bwd_vs_autograd).  (A reference with keys and values swapped is 1.6 of max |ref| away on opt_prefix.)"""
+    g = torch.Generator().manual_seed(11)
+    c = _attention_case(name, g, lambda t: t)
+    desc, H, dh, keep = c["desc"], c["H"], c["dh"], c["keep"]
+    if name == "vit":
+        dq = dev(c["qkv"])
+        views = (dq[:, :H * dh], dq[:, H * dh:2 * H * dh], dq[:, 2 * H * dh:])
+    else:
+        views = tuple(dev(t) for t in (c["q"], c["k"], c["v"]))
+    assert all(t.dtype == torch.float32 for t in views)
+    ref = _ref_attention(c["q"], c["k"], c["v"], desc, H, dh, c["scale"], c["causal"], dtype=torch.float64)
+    d = torch.tensor(desc, dtype=torch.int32, device="cuda")
+    out = L.attention(views[0], views[1], views[2], d, len(desc), max(x[1] for x in desc), H, dh, c["scale"], c["causal"])
+    assert out.dtype == torch.float32
+    err = (out.double().cpu()[keep] - ref[keep]).abs().max().item() / ref[keep].abs().max().item()
+    print("attention f32 %s: max |err| / max |ref| %.3g" % (name, err))
+    assert err < 2e-5, err
+
+
 def test_patch_embed_and_assemble(L):
     g = torch.Generator().manual_seed(2)
     B, S, P, D = 2, 28, 14, 48
@@ -279,6 +318,10 @@ def test_patch_embed_and_assemble(L):
     wp = torch.zeros(D, Kpad)
     wp[:, :Kreal] = w.reshape(D, -1)
     cols = L.im2col_patches(dev(pix), P, Kpad)
+    cols32 = L.im2col_patches(dev(pix), P, Kpad, dtype=torch.float32)       # devqa_im2col_patches_f32: the same layout, unrounded
+    assert torch.equal(cols32.to(torch.bfloat16), cols)
+    ref_cols = torch.nn.functional.unfold(pix, P, stride=P).transpose(1, 2).reshape(-1, Kreal)
+    assert torch.equal(cols32.cpu()[:, :Kreal], ref_cols) and float(cols32[:, Kreal:].abs().max()) == 0.0
     out = L.gemm(cols, dev(wp).to(torch.bfloat16), dev(b), want="f32")
     np.testing.assert_allclose(out.cpu().numpy().reshape(B, -1, D), ref.numpy(), atol=1e-4, rtol=1e-4)
     cls = torch.randn(D, generator=g)
@@ -300,6 +343,9 @@ def test_embed_rows_and_gather(L):
     out = L.embed_rows(dev(token), dev(src), dev(pos), dev(emb).to(torch.bfloat16), dev(img), dev(post).to(torch.bfloat16))
     ref = torch.cat([img, emb[token[8:].long()]]) + post[pos.long() + 2]
     np.testing.assert_allclose(out.cpu().numpy(), ref.numpy(), atol=1e-6)
+    emb32, post32 = torch.randn(V, D, generator=g), torch.randn(npos, D, generator=g)       # devqa_embed_rows_f32: unrounded fp32 tables
+    out32 = L.embed_rows(dev(token), dev(src), dev(pos), dev(emb32), dev(img), dev(post32))
+    assert torch.equal(out32.cpu(), torch.cat([img, emb32[token[8:].long()]]) + post32[pos.long() + 2])
     idx = torch.tensor([3, 0, 11, 3], dtype=torch.int32)
     got = L.gather_rows(out, dev(idx))
     np.testing.assert_array_equal(got.cpu().numpy(), out.cpu().numpy()[idx.numpy()])
@@ -323,6 +369,10 @@ def test_vocab_rows(L, R, V):
     ref_dl[torch.arange(R), labels.long()] -= 1
     ref_dl *= coef[:, None]
     np.testing.assert_allclose(dl.float().cpu().numpy(), ref_dl.numpy(), atol=1e-5, rtol=1e-2)
+    am32, nll32, dl32 = L.vocab_rows(dev(logits), dev(labels), dev(coef), True, True, True, dlogits_dtype=torch.float32)   # devqa_vocab_rows_f32
+    assert torch.equal(am32, am) and torch.equal(nll32, nll) and dl32.dtype == torch.float32
+    np.testing.assert_allclose(dl32.cpu().numpy(), ref_dl.numpy(), atol=1e-6, rtol=1e-4)
+    assert torch.equal(dl32.to(torch.bfloat16), dl)
 
 
 # Lmax > 16: the wide kernel (a-rows re-read per column step), 17..32 and 33..64 instantiations.  form: "matrix" = devqa_ft_adamw_step (first-moment
@@ -743,3 +793,41 @@ def test_attention_bwd_vs_autograd(L, kind, dtype):
     for got, ref in zip((dq, dk, dv), refs):
         err = (got.double() - ref.grad).abs().max().item() / max(ref.grad.abs().max().item(), 1e-9)
         assert err < tol, (kind, dtype, err)
+
+
+def test_profile_slots_count_launches(L):
+    """devqa_profile / devqa_profile_read / devqa_profile_dropped and the older devqa_profile_gemm pair (slots 0..3 of the same recorder):
+    one record per instrumented call while recording; 1 starts a new recording, 2 resumes one, 0 pauses."""
+    M, D = 8, 64
+    x, gamma, beta = torch.randn(M, D, device="cuda"), torch.ones(D, device="cuda"), torch.zeros(D, device="cuda")
+    a = torch.randn(64, 64, device="cuda").to(torch.bfloat16)
+    L.profile(1)
+    for _ in range(3):
+        L.layernorm(x, gamma, beta, 1e-5, want="f32")
+    L.profile(0)
+    L.layernorm(x, gamma, beta, 1e-5, want="f32")         # paused: not recorded
+    L.profile(2)
+    L.layernorm(x, gamma, beta, 1e-5, want="f32")         # resumed: added to the three
+    L.profile(0)
+    ms, work, n = L.profile_read(L.PROF_LAYERNORM)
+    assert n == 4 and ms > 0 and work > 0 and L.profile_dropped() == 0
+    assert sum(r[2] for r in L.profile_gemm_read()) == 0
+    L.profile_gemm(1)                                     # a new recording: the layernorm records are gone
+    L.gemm(a, a)
+    L.profile_gemm(0)
+    rows = L.profile_gemm_read()
+    assert len(rows) == 4 and sum(r[2] for r in rows) >= 1 and sum(r[1] for r in rows) >= 2.0 * 64 * 64 * 64
+    assert L.profile_read(L.PROF_LAYERNORM)[2] == 0
+
+
+@pytest.mark.parametrize("n", [3, 1024, 4099])           # the scalar tail alone; whole 16-byte pieces; pieces + tail past one block
+def test_split_f32_bf16x2(L, n):
+    """devqa_split_f32_bf16x2: hi = bf16(x), lo = bf16(x - hi), bit for bit -- so hi + lo carries 16 mantissa bits of x"""
+    g = torch.Generator().manual_seed(n)
+    x = (torch.randn(n, generator=g) * 3).cuda()
+    hi, lo = torch.empty(n, dtype=torch.bfloat16, device="cuda"), torch.empty(n, dtype=torch.bfloat16, device="cuda")
+    import ctypes
+    L._chk(L.load().devqa_split_f32_bf16x2(L._p(x), L._p(hi), L._p(lo), ctypes.c_int64(n), L._stream()), "devqa_split_f32_bf16x2")
+    rhi = x.to(torch.bfloat16)
+    assert torch.equal(hi, rhi) and torch.equal(lo, (x - rhi.float()).to(torch.bfloat16))
+    assert float(((hi.float() + lo.float()) - x).abs().max()) <= 2.0 ** -16 * float(x.abs().max())

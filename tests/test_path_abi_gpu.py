@@ -277,6 +277,47 @@ def test_path_level_error_behaviour(tiny):
     assert L.devqa_ctx_destroy(ctypes.c_uint64(fresh.h or 0)) == -5                  # double destroy is refused, not a crash
 
 
+def test_llm_forward_short_form(tiny):
+    """devqa_llm_forward, the form without rotary positions, is devqa_llm_forward_ex with NULL positions (the wrapper's call): same bits"""
+    vllm, _, _, rec, _ = tiny
+    H = Host(vllm)
+    L = H.lib.load()
+    d0 = rec[0]["requests"][0]
+    x, desc, max_len, spans = H.pack([H.probe(d0["prompt"], None, " " + d0["target_new"])])
+    R = x.shape[0]
+    want = torch.tensor([R - 2, R - 1], dtype=torch.int32, device=H.dev)
+    ref = H.ctx.llm_forward(x.clone(), desc, 1, max_len, True, want)
+    out = torch.empty_like(ref)
+    n = L.devqa_llm_forward_workspace(H.ctx.h, R, 2)
+    ws = torch.empty(n + 256, dtype=torch.uint8, device=H.dev)
+    p = ws.data_ptr() + (-ws.data_ptr()) % 256
+    rc = L.devqa_llm_forward(H.ctx.h, x.data_ptr(), desc.data_ptr(), 1, max_len, R, 1, want.data_ptr(), 2, out.data_ptr(), ctypes.c_void_p(p), n, None)
+    torch.cuda.synchronize()
+    assert rc == 0 and torch.equal(out, ref)
+
+
+def test_ctx_set_weight_repoints_one_entry(tiny):
+    """devqa_ctx_set_weight: the schedules read the new storage from the next call on and the old one again after pointing back; a name
+    the table does not hold is refused."""
+    from devqa_amd import lib
+    vllm = tiny[0]
+    ctx = vllm.engine.path_ctx()
+    table = dict(vllm.model.weight_table())
+    fresh = lib.PathContext(0, ctx.desc, table)
+    pix = torch.randn((1, 3, ctx.desc.image_size, ctx.desc.image_size), generator=torch.Generator().manual_seed(3)).cuda()
+    base = fresh.vision_encode(pix)
+    w, b = table["language_projection.weight"], table["language_projection.bias"]
+    zero = torch.zeros_like(w)
+    fresh.set_weight("language_projection.weight", zero)
+    out = fresh.vision_encode(pix)
+    assert not torch.equal(out, base) and torch.equal(out, b.float().expand_as(out))      # 0 . x + bias
+    fresh.set_weight("language_projection.weight", w)
+    assert torch.equal(fresh.vision_encode(pix), base)
+    with pytest.raises(lib.DevqaError, match="no entry"):
+        fresh.set_weight("no.such.weight", zero)
+    fresh.close()
+
+
 def test_gather_scores_single_rank():
     """devqa_comm_* / devqa_gather_scores with a one-rank communicator (the N > 1 launch is the driver's; rank logic: test_dist_cpu)."""
     from devqa_amd import lib
@@ -296,8 +337,12 @@ def test_gather_scores_single_rank():
 
 
 def test_mend_transform_and_apply_entry_points():
-    """devqa_mend_transform (K16) against the op-level composition it sequences and a float64 restatement of
-    GradientTransform / LRLinear (auxiliary_networks.py:112-151, 62-83); devqa_mend_apply (K17) against h @ (xt^T dt)."""
+    """devqa_mend_transform (K16) against the op-level composition it sequences, bit for bit, and against a float64 restatement of
+    GradientTransform / LRLinear (auxiliary_networks.py:112-151, 62-83: clamp((x v^T u^T + bias) * scale + shift, min=0) + x) with half the
+    mode scales negative, where relu(pre) * scale + shift would be far off: max |err| / max |ref| < 1e-4, the exact-fp32 GEMM's 2e-5
+    (test_gemm_f32_exact_and_splitk) over the four chained GEMMs (the test prints the figure it measures; the ReLU-then-scale form is
+    1.0 of max |ref| away on these inputs);
+    devqa_mend_apply (K17) against h @ (xt^T dt)."""
     import devqa_amd  # noqa: F401
     from devqa_amd import lib
     g = torch.Generator().manual_seed(5)
@@ -307,7 +352,8 @@ def test_mend_transform_and_apply_entry_points():
     idx = torch.tensor([0, 2, 3, 7], dtype=torch.int32)
     stats = [torch.randn(du, generator=g), torch.rand(du, generator=g) + 0.5, torch.randn(dv, generator=g), torch.rand(dv, generator=g) + 0.5]
     layers = [{"u": torch.randn(D, rank, generator=g) * 0.2, "v": torch.randn(rank, D, generator=g) * 0.2, "bias": torch.randn(D, generator=g) * 0.1,
-               "mode_scale": torch.rand(D, generator=g) + 0.5, "mode_shift": torch.randn(D, generator=g) * 0.1} for _ in range(nl)]
+               "mode_scale": (torch.rand(D, generator=g) + 0.5) * (1 - 2 * (torch.arange(D) % 2)),      # every other one negative
+               "mode_shift": torch.randn(D, generator=g) * 0.1} for _ in range(nl)]
     cu = lambda t: t.cuda().contiguous()  # noqa: E731
     ox, od = lib.mend_transform(cu(x), cu(dl), cu(idx), [{k: cu(v) for k, v in L_.items()} for L_ in layers], [cu(t) for t in stats])
     # float64 restatement
@@ -316,8 +362,11 @@ def test_mend_transform_and_apply_entry_points():
                      (dl[sel].double() - stats[2].double()) / (stats[3].double() + 1e-7)], 1)
     for L_ in layers:
         pre = inp @ L_["v"].double().T @ L_["u"].double().T + L_["bias"].double()
-        inp = inp + torch.relu(pre) * L_["mode_scale"].double() + L_["mode_shift"].double()
-    # the epilogue's exact formula is the op-level kernel's (tests/test_mend_gpu.py pins it to the reference); here: same composition
+        inp = torch.clamp(pre * L_["mode_scale"].double() + L_["mode_shift"].double(), min=0) + inp
+    err64 = float((torch.cat([ox, od], 1).double().cpu() - inp).abs().max() / inp.abs().max())
+    print("mend_transform against float64: max |err| / max |ref| %.3g" % err64)
+    assert err64 < 1e-4
+    # the same composition from the op-level kernels (tests/test_mend_train_ops_gpu.py holds each of them to float64 on its own): bit for bit
     inp32 = lib.mend_normalize_concat(cu(x), cu(dl), cu(idx), *[cu(t) for t in stats], 1e-7)
     for L_ in layers:
         prea = lib.gemm(lib.gemm(inp32, cu(L_["v"])), cu(L_["u"]))
