@@ -13,8 +13,11 @@ reference's relative layout, so the reference's command lines parse unchanged:
                          nothing is unpickled)
   --queries     optional .npz {sentences, embeddings}: pre-computed sentence embeddings (a lookup-table "encoder")
   --encoder     optional "package.module:callable" -- the user's sentence encoder, list[str] -> float32 [n, D]
-                (all-MiniLM-L6-v2 / multi-qa-mpnet-base-dot-v1 through sentence_transformers in the reference; neither is
-                available offline, and the reference's README allows "your own retriever")
+                (all-MiniLM-L6-v2 / multi-qa-mpnet-base-dot-v1 through sentence_transformers in the reference; the
+                reference's README allows "your own retriever")
+  --sentence_model_path  optional BERT-family sentence-encoder directory (sentence-transformers or plain HF layout, e.g.
+                all-MiniLM-L6-v2): the native SentenceEncoder then encodes free text on the device; used when neither --encoder nor
+                --queries is given
   --ike_corpus  optional .npz {sentences, embeddings} for IKE_VL (default: --embeddings when it carries `sentences`)
   --tp_texts    optional text file, one locality sentence per line, for TP_VL
 <data root> = $DEVQA_DATA_ROOT or ./data.
@@ -41,6 +44,7 @@ def add_data_args(p):
     p.add_argument("--embeddings", type=str, default=None)
     p.add_argument("--queries", type=str, default=None)
     p.add_argument("--encoder", type=str, default=None)
+    p.add_argument("--sentence_model_path", type=str, default=None)
     p.add_argument("--ike_corpus", type=str, default=None)
     p.add_argument("--tp_texts", type=str, default=None)
     p.add_argument("--dtype", type=str, default="bf16")
@@ -59,7 +63,8 @@ def resolve_paths(cfg, split):
 
 
 def load_encoder(cfg):
-    """The sentence encoder of this run: --encoder "module:callable", else the --queries lookup table, else None."""
+    """The sentence encoder of this run: --encoder "module:callable", else the --queries lookup table, else the native encoder of
+    --sentence_model_path, else None."""
     if getattr(cfg, "encoder", None):
         mod, _, fn = cfg.encoder.partition(":")
         if not fn:
@@ -75,6 +80,13 @@ def load_encoder(cfg):
             except KeyError as e:
                 raise BaseException("no pre-computed embedding for %r in %s (pass --encoder for free text)" % (e.args[0], cfg.queries))
         return lookup
+    if getattr(cfg, "sentence_model_path", None):
+        enc = getattr(cfg, "_sentence_encoder", None)      # the dataset builder and the editor share ONE encoder (one copy of the weights)
+        if enc is None:
+            from .text_encoder import SentenceEncoder
+            enc = SentenceEncoder(cfg.sentence_model_path, cfg.device, "fp32" if getattr(cfg, "dtype", "bf16") == "fp32" else "bf16")
+            cfg._sentence_encoder = enc
+        return enc
     return None
 
 
@@ -84,8 +96,8 @@ def build_dataset(cfg, split):
     data_path, img_root, emb = resolve_paths(cfg, split)
     enc = load_encoder(cfg)
     if enc is None:
-        raise BaseException("the dynamic-evaluation builder needs a sentence encoder: pass --encoder module:callable or --queries "
-                            "<npz of pre-computed sentence embeddings> (the reference's all-MiniLM-L6-v2 checkpoint is not here)")
+        raise BaseException("the dynamic-evaluation builder needs a sentence encoder: pass --sentence_model_path <BERT-family model "
+                            "directory>, --encoder module:callable or --queries <npz of pre-computed sentence embeddings>")
     if not os.path.exists(emb):
         raise BaseException("retrieval corpus %s not found (pass --embeddings; build one with devqa_amd.dataset.vllm.save_corpus)" % emb)
     corpus = np.load(emb, allow_pickle=False)
@@ -103,7 +115,7 @@ def editor_kwargs(cfg):
     if name in ("ike_vl", "lte_vl"):
         enc = load_encoder(cfg)
         if enc is None:
-            raise BaseException("%s needs a sentence encoder: pass --encoder module:callable or --queries <npz>" % name)
+            raise BaseException("%s needs a sentence encoder: pass --sentence_model_path <dir>, --encoder module:callable or --queries <npz>" % name)
         kw["encode"] = enc
     if name == "ike_vl":
         path = cfg.ike_corpus or resolve_paths(cfg, "eval")[2]

@@ -3,8 +3,9 @@
 BaseVLLMEditData keeps the reference's two views (`data_with_img`, `data_with_img_path`; images
 stay PATH strings, vllm.py:44-52).  The probe recipe of `__init_eic_evqa__` (vllm.py:121-228) and
 the EVQA/VLKEB prompt suffixing (vllm.py:231-297) are restated in `build_probes`/`EVQA`/`VLKEB`
-with a pluggable retriever, because the reference hard-codes a SentenceTransformer checkpoint and
-pickled embeddings that do not exist offline (README allows "your own retriever").
+with a pluggable retriever, because the reference hard-codes a SentenceTransformer checkpoint path and
+pickled embeddings (README allows "your own retriever"); `sentence_model_path` builds the native
+SentenceEncoder (text_encoder.py) from a BERT-family model directory instead of a user callable.
 Retrieval itself (normalise -> dot -> top-k -> first hit whose answer differs) runs on the HIP
 cosine top-k kernel (devqa_cosine_topk).
 """
@@ -32,11 +33,17 @@ class BaseVLLMEditData(BaseEditData):
 class EmbeddingRetriever:
     """finds_sim (vllm.py:65-87) over a stored corpus {sentences, images, prompts, embeddings}
     (the on-disk dict layout of the reference's pickles, passed in as arrays/lists).
-    `encode(list[str]) -> float32 [n, D]` is the user's sentence encoder."""
+    `encode(list[str]) -> float32 [n, D]` is the user's sentence encoder; with encode=None, `sentence_model_path` (a BERT-family
+    model directory) is loaded into the native SentenceEncoder, whose query embeddings stay on the device."""
 
     def __init__(self, encode: Callable[[Sequence[str]], np.ndarray], embeddings: np.ndarray, prompts: List,
-                 images: List[str], device="cuda:0"):
+                 images: List[str], device="cuda:0", sentence_model_path: str = None, dtype="bf16"):
         import torch
+        if encode is None:
+            if sentence_model_path is None:
+                raise RuntimeError("EmbeddingRetriever needs `encode` or `sentence_model_path`")
+            from ..text_encoder import SentenceEncoder
+            encode = SentenceEncoder(sentence_model_path, device, dtype)
         self.encode = encode
         self.prompts = prompts
         self.save_image_path = images
@@ -49,13 +56,16 @@ class EmbeddingRetriever:
     def topk(self, queries: np.ndarray, tops=5):
         import torch
         from .. import lib
-        q = torch.as_tensor(np.asarray(queries, np.float32)).to(self.device).contiguous()
+        if isinstance(queries, torch.Tensor) and queries.is_cuda:
+            q = queries.to(torch.float32).contiguous()
+        else:
+            q = torch.as_tensor(np.asarray(queries, np.float32)).to(self.device).contiguous()
         idx, _ = lib.cosine_topk(self.stored, q, tops, True, True, corpus_inv_norm=self.stored_inv_norm)
         return idx.cpu().numpy()
 
     def finds_sim_many(self, srcs: List[str], trgs: List[str], tops=5):
         """Batched finds_sim: one kernel launch for all records."""
-        hits = self.topk(self.encode(srcs), tops)
+        hits = self.topk(getattr(self.encode, "encode_device", self.encode)(srcs), tops)
         out = []
         for hit, trg in zip(hits, trgs):
             pick = None
@@ -160,9 +170,17 @@ class EVQA(BaseVLLMEditData):
     """vllm.py:231-254: every prompt gets ' The answer is:'; text_loc additionally '?' AFTER it."""
 
     def __init__(self, data_path: str = "data/easy-edit-mm/vqa/vqa_train.json", img_root_dir: str = "data/easy-edit-mm/images",
-                 data_n=None, retriever: Optional[EmbeddingRetriever] = None) -> None:
+                 data_n=None, retriever: Optional[EmbeddingRetriever] = None, sentence_model_path: str = None,
+                 corpus=None, device="cuda:0") -> None:
         if "vqa" not in os.path.basename(data_path):
             raise RuntimeError("not a vqa file")
+        if retriever is None and sentence_model_path is not None and corpus is not None:
+            # the reference's own route (vllm.py:91-104): the sentence model plus the stored corpus (a dict or a file of one)
+            c = load_corpus(corpus) if isinstance(corpus, (str, os.PathLike)) else corpus
+            retriever = EmbeddingRetriever(None, c["embeddings"], c["prompts"], c["images"], device, sentence_model_path)
+        if retriever is None and sentence_model_path is not None:
+            raise RuntimeError("EVQA: sentence_model_path also needs corpus= (the stored {sentences, images, prompts, embeddings} dict or "
+                               "its .npz / pickle; tools/encode_corpus.py writes one)")
         if retriever is None:
             raise RuntimeError("EVQA needs a retriever (the reference's hard-coded SentenceTransformer path does not exist here)")
         recs = _load_records(data_path, data_n)

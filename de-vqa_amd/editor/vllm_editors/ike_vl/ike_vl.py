@@ -12,7 +12,9 @@ cosine top-k kernel (devqa_cosine_topk) and installs a text transform on the wra
 `get_llm_input_embeds` -- the same hook mechanism the reference's retrieval editors use
 (R/editor/vllm_editors/lte_vl/lte_vl.py:75-92); `restore_to_original_model` removes it.  Label rows are
 the LAST L positions, so prepending context leaves the evaluator's label/mask bookkeeping intact.
-The sentence encoder (all-MiniLM-L6-v2 in the reference, unavailable offline) is a constructor argument.
+The sentence encoder (all-MiniLM-L6-v2 in the reference) is the native `SentenceEncoder` (text_encoder.py) built from
+`IKEvlConfig.sentence_model_path`, a BERT-family model directory, or any `encode(list[str]) -> [n, D]` callable passed to the
+constructor; with the native encoder the query embedding never leaves the device.
 """
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Sequence, Tuple
@@ -29,6 +31,7 @@ from .... import lib
 class IKEvlConfig(BaseConfig):
     edit_model_name: str
     k: int = 32                      # IKEMultimodalHyperParams.k (ike_hparams.py:38)
+    sentence_model_path: str = None  # BERT-family sentence-encoder directory (IKEMultimodalHyperParams.sentence_model_name); None: pass `encode`
 
 
 def ike_sentence(new_fact: str, prompt_and_answer: str) -> str:
@@ -56,6 +59,10 @@ class IKEvl(VLLMBaseEditor):
                  encode: Callable[[Sequence[str]], np.ndarray] = None):
         super().__init__(vllm, device)
         self.cfg = config
+        if encode is None and corpus is not None:
+            from ....text_encoder import SentenceEncoder, is_bert_dir, mode_of
+            if is_bert_dir(getattr(config, "sentence_model_path", None)):
+                encode = SentenceEncoder(config.sentence_model_path, self.device, mode_of(vllm))
         if corpus is None or encode is None:
             raise RuntimeError("IKEvl needs the stored corpus {sentences, embeddings} and a sentence encoder")
         self.encode = encode
@@ -84,14 +91,15 @@ class IKEvl(VLLMBaseEditor):
         if side is None and torch.device(self.device).type == "cuda":
             side = self._retr_stream = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))       # (the corpus and its norms were written on the main stream)
-        q_host = torch.as_tensor(np.asarray(self.encode([query]), np.float32))
+        on_device = getattr(self.encode, "encode_device", None)      # the native encoder: no host round trip for the query
+        q_host = None if on_device else torch.as_tensor(np.asarray(self.encode([query]), np.float32))
         if side is not None:
             with torch.cuda.stream(side):
-                q = lib.h2d(q_host, torch.float32, self.device).contiguous()
+                q = on_device([query]) if on_device else lib.h2d(q_host, torch.float32, self.device).contiguous()
                 idx, _ = lib.cosine_topk(self.stored, q, k, True, True, corpus_inv_norm=self.stored_inv_norm)   # normalize_embeddings + semantic_search(dot)
                 ids = idx[0].cpu().tolist()
         else:
-            q = q_host.to(self.device).contiguous()
+            q = on_device([query]) if on_device else q_host.to(self.device).contiguous()
             idx, _ = lib.cosine_topk(self.stored, q, k, True, True, corpus_inv_norm=self.stored_inv_norm)
             ids = idx[0].tolist()
         icl = [self.stored_sentences[int(i)] for i in ids]

@@ -12,8 +12,10 @@ from the logits (:75-92).
 Two things differ from the reference in HOW, not WHAT:
   * `probe_prefix` exposes the same retrieval to the evaluator's batched probe path (vllm_editor_eval._argmax_many), so
     the 12 post-edit probes of a sample still share one decoder pass; the per-probe hook stays for every other caller;
-  * the sentence encoder (`multi-qa-mpnet-base-dot-v1` through sentence_transformers in the reference, :50; neither is
-    available offline) is a constructor argument `encode(list[str]) -> [n, retrieval_embed_dim]`.
+  * the sentence encoder (`multi-qa-mpnet-base-dot-v1` through sentence_transformers in the reference, :50) is a constructor
+    argument `encode(list[str]) -> [n, retrieval_embed_dim]`; without it, a `retriever_path` that is a BERT-family model directory
+    is loaded into the native `SentenceEncoder` (text_encoder.py).  MPNet itself (relative-position attention bias) is not
+    supported there, so the shipped configs still need a user encoder.
 
 Training (:152-233): the reference fine-tunes `fine_tune_modules_path` (the shipped configs: the whole
 `language_model`) with Adam at lr 5e-6 on in-context edit prompts -- per step one reliability and two generality label losses on
@@ -79,6 +81,14 @@ class LTEvl(VLLMBaseEditorWithTraining):
             self.vllm_proc_data = vllm_proc_data
             self.device_proc_data = device_proc_data
         if encode is None:
+            from ....text_encoder import SentenceEncoder, is_bert_dir, mode_of
+            if is_bert_dir(config.retriever_path):
+                encode = SentenceEncoder(config.retriever_path, self.device, mode_of(vllm))
+        dim = getattr(encode, "dim", None)
+        if dim is not None and dim != config.retrieval_embed_dim:      # known now: do not wait for the first edit's _embed to say so
+            raise RuntimeError("LTEvl: the sentence encoder gives %d-d embeddings, retrieval_embed_dim is %d (set it to the encoder's)"
+                               % (dim, config.retrieval_embed_dim))
+        if encode is None:
             raise RuntimeError("LTEvl needs `encode`: list[str] -> [n, %d] sentence embeddings (the reference uses "
                                "SentenceTransformer(%r))" % (config.retrieval_embed_dim, config.retriever_path))
         self.encode = encode
@@ -90,10 +100,11 @@ class LTEvl(VLLMBaseEditorWithTraining):
 
     # ------------------------------------------------------------------------------------------------------------
     def _embed(self, texts: List[str]) -> torch.Tensor:
-        e = np.asarray(self.encode(texts), np.float32)
+        on_device = getattr(self.encode, "encode_device", None)      # the native encoder: the embedding stays on the device
+        e = on_device(texts) if on_device else np.asarray(self.encode(texts), np.float32)
         if e.ndim != 2 or e.shape[1] != self.cfg.retrieval_embed_dim:
-            raise RuntimeError("encoder returned %s, expected [n, %d]" % (e.shape, self.cfg.retrieval_embed_dim))
-        return torch.from_numpy(e).to(self.device).contiguous()
+            raise RuntimeError("encoder returned %s, expected [n, %d]" % (tuple(e.shape), self.cfg.retrieval_embed_dim))
+        return e if on_device else torch.from_numpy(e).to(self.device).contiguous()
 
     def wrap_get_llm_outpt(self):  # lte_vl.py:75-92
         def wrap(get_llm_outpt):

@@ -144,6 +144,10 @@ def load():
     _sig(L.devqa_comm_create, [I, I, P, I, P])
     _sig(L.devqa_comm_destroy, [U64])
     _sig(L.devqa_gather_scores, [U64, P, I, P, P])
+    # ---- sentence encoder (include/devqa_text.h, csrc/text_ops.hip) ----
+    _sig(L.devqa_text_embed_ln, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P])
+    _sig(L.devqa_text_embed_ln_f32, [P, P, P, P, P, P, P, I, I, I, I, F, P, P, P])
+    _sig(L.devqa_seq_pool, [P, P, P, I, I, I, I, I, P, P])
     _lib = L
     return L
 
@@ -167,6 +171,8 @@ EXPORTS = ["devqa_ctx_create", "devqa_ctx_destroy", "devqa_ctx_set_weight", "dev
            "devqa_mend_lrlinear_bwd", "devqa_sumsq_f32", "devqa_adam_step", "devqa_tp_neuron_fwd", "devqa_tp_neuron_bwd",
            "devqa_tp_gated_neuron_fwd", "devqa_tp_gated_neuron_bwd",
            "devqa_swiglu_bwd_bf16", "devqa_swiglu_bwd_f32"]
+# the entry points of include/devqa_text.h (the sentence encoder's own kernels)
+EXPORTS_TEXT = ["devqa_text_embed_ln", "devqa_text_embed_ln_f32", "devqa_seq_pool"]
 
 
 def gemm_rows_longk(a, w):
@@ -1204,3 +1210,45 @@ class ScoreComm:
         if self.h:
             _chk(load().devqa_comm_destroy(self.h), "devqa_comm_destroy")
             self.h = None
+
+
+# ---- sentence encoder (include/devqa_text.h) ----
+POOL_MEAN, POOL_CLS, POOL_MAX = 0, 1, 2
+
+
+def text_embed_ln(token, pos, word, position, type0, gamma, beta, eps, want="both"):
+    """LN((word[token] + type0) + position[pos]) of int32 [R] ids -> bf16 and / or fp32 [R, D] (BertEmbeddings in one pass).
+    The tables are both bf16 or both fp32; ids outside their table are the caller's to reject on the host."""
+    assert token.dtype == torch.int32 and pos.dtype == torch.int32 and token.is_cuda and pos.is_cuda and token.numel() == pos.numel()
+    assert word.dtype == position.dtype == type0.dtype and word.dtype in (torch.bfloat16, torch.float32)
+    for t, n in ((word, "word"), (position, "position"), (type0, "type0")):
+        _need(t, word.dtype, "text_embed_ln " + n)
+    _need(gamma, torch.float32, "text_embed_ln gamma")
+    _need(beta, torch.float32, "text_embed_ln beta")
+    R, (V, D), P = token.numel(), word.shape, position.shape[0]
+    assert position.shape[1] == D and type0.numel() == D and gamma.numel() == D and beta.numel() == D
+    ob = torch.empty((R, D), dtype=torch.bfloat16, device=word.device) if want in ("bf16", "both") else None
+    of = torch.empty((R, D), dtype=torch.float32, device=word.device) if want in ("f32", "both") else None
+    fn = load().devqa_text_embed_ln if word.dtype == torch.bfloat16 else load().devqa_text_embed_ln_f32
+    _chk(fn(_p(token), _p(pos), _p(word), _p(position), _p(type0), _p(gamma), _p(beta), R, D, V, P, float(eps), _p(ob), _p(of), _stream()),
+         "devqa_text_embed_ln")
+    if want == "both":
+        return ob, of
+    return ob if ob is not None else of
+
+
+def seq_pool(x, seq_start, seq_len, mode=POOL_MEAN, normalize=False, out=None):
+    """fp32 [S, D] sentence vectors of the packed rows x fp32 [R, D]: mean / first row / column max of rows
+    [seq_start[s], seq_start[s] + seq_len[s]), optionally L2-normalised.  The same bits on every run."""
+    _need(x, torch.float32, "seq_pool x")
+    assert seq_start.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_start.is_cuda and seq_len.is_cuda
+    S = seq_start.numel()
+    assert seq_len.numel() == S and x.dim() == 2
+    R, D = x.shape
+    if out is None:
+        out = torch.empty((S, D), dtype=torch.float32, device=x.device)
+    _need(out, torch.float32, "seq_pool out")
+    assert out.shape == (S, D)
+    _chk(load().devqa_seq_pool(_p(x), _p(seq_start), _p(seq_len), R, S, D, int(mode), int(bool(normalize)), _p(out), _stream()),
+         "devqa_seq_pool")
+    return out

@@ -161,3 +161,31 @@ def mend_aux_init(name: str, shape, seed: int = 7) -> np.ndarray:
     if leaf == "v":   # [rank, inf]
         return (1.0 / np.sqrt(shape[1]) * z).astype(np.float32)
     return (0.02 * z).astype(np.float32)
+
+
+def bert_param_shapes(cfg: dict):
+    """{HF BertModel parameter name: shape} of a BERT-family text tower (the pooler head is not part of a sentence encoder)."""
+    D, F = int(cfg["hidden_size"]), int(cfg["intermediate_size"])
+    out = {"embeddings.word_embeddings.weight": (int(cfg["vocab_size"]), D),
+           "embeddings.position_embeddings.weight": (int(cfg["max_position_embeddings"]), D),
+           "embeddings.token_type_embeddings.weight": (int(cfg.get("type_vocab_size", 2)), D),
+           "embeddings.LayerNorm.weight": (D,), "embeddings.LayerNorm.bias": (D,)}
+    for i in range(int(cfg["num_hidden_layers"])):
+        p = "encoder.layer.%d." % i
+        for lin, (o, k) in (("attention.self.query", (D, D)), ("attention.self.key", (D, D)), ("attention.self.value", (D, D)),
+                            ("attention.output.dense", (D, D)), ("intermediate.dense", (F, D)), ("output.dense", (D, F))):
+            out[p + lin + ".weight"], out[p + lin + ".bias"] = (o, k), (o,)
+        for ln in ("attention.output.LayerNorm", "output.LayerNorm"):
+            out[p + ln + ".weight"], out[p + ln + ".bias"] = (D,), (D,)
+    return out
+
+
+def bert_param_init(name: str, shape, seed: int = 20251121, std: float = 0.1) -> np.ndarray:
+    """Sentence-encoder fixture weights: every parameter std * N(0, 1) from default_rng([seed, crc32(name)]), LayerNorm gains
+    1 + std * N(0, 1).  At std 0.1 (not BERT's 0.02) a tanh GELU or a LayerNorm eps of 1e-5 moves the embedding by more than the fp32
+    bar, so a fixture with these weights can tell them from the right arithmetic (tests/test_text_encoder_cpu.py lists the distances)."""
+    rng = np.random.default_rng([seed, zlib.crc32(name.encode())])
+    z = rng.standard_normal(tuple(int(s) for s in shape), dtype=np.float32)
+    if "LayerNorm" in name and name.endswith("weight"):
+        return (1.0 + std * z).astype(np.float32)
+    return (std * z).astype(np.float32)

@@ -71,16 +71,20 @@ def load_vllm_for_edit(model_name: str, device: str, dtype="bf16"):  # :111-124
 
 
 def load_vllm_editor(editor_name: str, edit_model_name: str, device, extra_devices: List[int] = [1],
-                     editor_ckpt_path=None, for_train=False, dtype="bf16", **editor_kwargs):  # :126-175
+                     editor_ckpt_path=None, for_train=False, dtype="bf16", sentence_model_path=None, **editor_kwargs):  # :126-175
     editor_name = editor_name.lower()
     config_path = get_editor_config_path(editor_name, edit_model_name)
     vllm = load_vllm_for_edit(edit_model_name, device, dtype)
     if editor_name == "ft_vl":
         from ..editor.vllm_editors.ft_vl.ft_vl import FTvl, FTvlConfig
         return FTvl(vllm, FTvlConfig.from_yaml(config_path), device)
-    if editor_name == "ike_vl":  # needs corpus={sentences, embeddings} and encode=callable (see ike_vl.py)
+    if editor_name == "ike_vl":  # needs corpus={sentences, embeddings} and a sentence encoder: sentence_model_path (a BERT-family
+        # directory, loaded into the native SentenceEncoder) or encode=callable (see ike_vl.py)
         from ..editor.vllm_editors.ike_vl.ike_vl import IKEvl, IKEvlConfig
-        return IKEvl(vllm, IKEvlConfig.from_yaml(config_path), device, **editor_kwargs)
+        cfg = IKEvlConfig.from_yaml(config_path)
+        if sentence_model_path is not None:
+            cfg.sentence_model_path = sentence_model_path
+        return IKEvl(vllm, cfg, device, **editor_kwargs)
     if editor_name == "mend_vl":  # editor_ckpt_path: a reference-format `Best` checkpoint of the trained hyper-network
         from ..editor.vllm_editors.mend_vl.mend_vl import MENDvl, MENDvlConfig
         return MENDvl(vllm, MENDvlConfig.from_yaml(config_path), device, ckpt_path=editor_ckpt_path, for_train=for_train,
@@ -88,12 +92,16 @@ def load_vllm_editor(editor_name: str, edit_model_name: str, device, extra_devic
     if editor_name == "tp_vl":   # needs locality_texts=[...] or locality_data_path=<text file> (the reference reads wikitext)
         from ..editor.vllm_editors.tp_vl.tp_vl import TPvl, TPvlConfig
         return TPvl(vllm, TPvlConfig.from_yaml(config_path), device, **editor_kwargs)
-    if editor_name == "lte_vl":  # needs encode=callable (the reference loads sentence_transformers' multi-qa-mpnet-base-dot-v1)
+    if editor_name == "lte_vl":  # sentence encoder: sentence_model_path / a retriever_path that is a BERT-family directory (native
+        # SentenceEncoder), or encode=callable (the reference loads sentence_transformers' multi-qa-mpnet-base-dot-v1: MPNet, not native)
         from ..editor.vllm_editors.lte_vl.lte_vl import LTEvl, LTEvlConfig
         # for_train (:159-162): a second, frozen copy of the model prepares the training batches (the reference puts it on
         # extra_devices[0]; one MI355X holds both, so it lives on the same device); a trained checkpoint is loaded below
         vllm_data_proc = load_vllm_for_edit(edit_model_name, device, dtype) if for_train else None
-        ed = LTEvl(vllm, LTEvlConfig.from_yaml(config_path), device, vllm_data_proc, device if for_train else None, **editor_kwargs)
+        cfg = LTEvlConfig.from_yaml(config_path)
+        if sentence_model_path is not None:
+            cfg.retriever_path = sentence_model_path
+        ed = LTEvl(vllm, cfg, device, vllm_data_proc, device if for_train else None, **editor_kwargs)
         if editor_ckpt_path is not None:      # :173-174
             ed.load_ckpt(editor_ckpt_path, True, False)
         return ed
