@@ -1,34 +1,23 @@
 // Packed varlen softmax attention (ViT self-attn, Q-Former self/cross-attn, OPT causal attn with an
-// optional shared image-token prefix).  See include/devqa.h for the sequence descriptor.
+// optional shared image-token prefix).  See include/devqa.h for the sequence descriptor.  The bf16 entry point checks its arguments
+// here and runs the MFMA kernels of attention_mfma.hip; the kernel in this file is the fp32 compute mode (devqa_attention_f32).
 //
 // v1 structure (correctness-first, VALU):  one workgroup = one (sequence, head, 16-query tile);
 // 4 waves x 4 query rows.  Keys/values stream through LDS in 64-key chunks (bf16 -> fp32, row
 // stride dh+1 so that lane=key reads are bank-conflict free); scores use lane = key, the PV
 // product uses lane = output channel; online softmax in fp32 (running max / sum per query row).
-#include <stdlib.h>
 #include "common.h"
 
 #define ATT_QT 16     // query rows per workgroup
 #define ATT_KC 64     // keys per chunk
 #define ATT_MAXDH 128
 
-__device__ __forceinline__ void load8(const bf16_t* p, float* o) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        o[2 * t] = bf16_to_f32(w[t] & 0xffff);
-        o[2 * t + 1] = bf16_to_f32(w[t] >> 16);
-    }
-}
 __device__ __forceinline__ void load8(const float* p, float* o) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
     o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
 }
-__device__ __forceinline__ float ld1(const bf16_t* p) { return bf16_to_f32(*p); }
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
-__device__ __forceinline__ void st1(bf16_t* p, float v) { *p = f32_to_bf16(v); }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 
 template <typename T>
@@ -196,15 +185,10 @@ int launch_attention_mfma(const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t
                           int64_t ldo, const int32_t* seq_desc, int n_seq, int max_q_len, int H, int dh, float scale,
                           int causal, void* stream);  // attention_mfma.hip
 
-// bf16: MFMA flash attention (attention_mfma.hip).  DEVQA_ATTENTION_VALU=1 selects the v1 VALU kernel
-// (kept as an in-library cross-check; same results up to fp reassociation).
+// bf16: MFMA flash attention (attention_mfma.hip)
 extern "C" int devqa_attention(const devqa_bf16* q, int64_t ldq, const devqa_bf16* k, int64_t ldk, const devqa_bf16* v,
                                int64_t ldv, devqa_bf16* out, int64_t ldo, const int32_t* seq_desc, int n_seq,
                                int max_q_len, int H, int dh, float scale, int causal, void* stream) {
-    static const bool use_valu = getenv("DEVQA_ATTENTION_VALU") != nullptr;
-    if (use_valu)
-        return launch_attention<bf16_t>(q, ldq, k, ldk, v, ldv, out, ldo, seq_desc, n_seq, max_q_len, H, dh, scale, causal,
-                                        stream);
     DEVQA_CHECK_ARG(q && k && v && out && seq_desc, "attention: null pointer");
     if (n_seq == 0 || max_q_len == 0) return DEVQA_OK;
     DEVQA_CHECK_SHAPE(n_seq > 0 && max_q_len > 0 && H > 0, "attention: bad dims");

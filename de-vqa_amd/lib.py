@@ -468,8 +468,8 @@ def colsum_(x, out, accumulate=True):
     _chk(load().devqa_colsum_f32(_p(x), M, D, int(bool(accumulate)), _p(out), _stream()), "devqa_colsum_f32")
 
 
-_ATT_ENV_KEYS = ("DEVQA_ATTENTION_DMA", "DEVQA_ATTENTION_NW", "DEVQA_ATTENTION_QB", "DEVQA_ATTENTION_DBUF", "DEVQA_ATTENTION_SHORT",
-                 "DEVQA_ATTENTION_RESIDENT", "DEVQA_ATTENTION_EXP", "DEVQA_ATTENTION_XCD", "DEVQA_ATTENTION_RING", "DEVQA_ATTENTION_FOLD", "DEVQA_ATTENTION_NBUF", "DEVQA_ATTENTION_PACK")
+_ATT_ENV_KEYS = ("DEVQA_ATTENTION_DMA", "DEVQA_ATTENTION_NW", "DEVQA_ATTENTION_SHORT", "DEVQA_ATTENTION_XCD", "DEVQA_ATTENTION_RING",
+                 "DEVQA_ATTENTION_FOLD")
 _att_env_seen = None
 
 
@@ -486,7 +486,8 @@ def attention_env_sync():
 
 def attention(q, k, v, seq_desc, n_seq, max_q_len, H, dh, scale, causal, out=None, self_full=False):
     """q,k,v: bf16 2-D views (rows x >=H*dh, unit inner stride). seq_desc int32 [n_seq,6] on device.
-    self_full=True promises plain non-causal self-attention for every sequence (kp_len == 0, ko_len == q_len): devqa.h, causal bit 2."""
+    self_full=True promises plain non-causal self-attention for every sequence (kp_len == 0, ko_len == q_len): devqa.h, causal bit 2
+    (accepted, no effect on the kernel choice)."""
     if self_full:
         assert not causal
         causal = 4

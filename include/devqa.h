@@ -144,8 +144,8 @@ int devqa_swiglu_f32(const float* gu, int R, int F, float* out, void* stream);
  * seq_desc: int32 [n_seq][6] = {q_start,q_len,kp_start,kp_len,ko_start,ko_len} (device).
  * max_q_len is the host-known max of q_len (grid sizing).  dh % 8 == 0, dh <= 128.
  * `causal`: bit 0 = the causal rule above; bit 2 (value 4) = a promise by the caller that EVERY sequence is plain non-causal
- * self-attention (kp_len == 0, ko_len == q_len, the ViT case), which lets short sequences take a kernel that keeps the whole
- * K / V of a sequence in LDS (descriptors live on the device, so the library cannot check this itself).
+ * self-attention (kp_len == 0, ko_len == q_len, the ViT case).  The bit is accepted and has no effect: the kernel it used to
+ * allow (whole K / V of a sequence in LDS) measured slower than the default and was removed.
  * Replaces eager/sdpa attention in HF Blip2Attention, Blip2QFormerMultiHeadAttention and
  * OPTAttention (same call sites as above).
  */
@@ -153,7 +153,7 @@ int devqa_attention(const devqa_bf16* q, int64_t ldq, const devqa_bf16* k, int64
                     int64_t ldv, devqa_bf16* out, int64_t ldo, const int32_t* seq_desc, int n_seq, int max_q_len,
                     int H, int dh, float scale, int causal, void* stream);
 
-/* The kernel-variant switches of devqa_attention (DEVQA_ATTENTION_DMA / _NW / _QB / _DBUF / _SHORT / _RESIDENT: A/B measurements and
+/* The kernel-variant switches of devqa_attention (DEVQA_ATTENTION_DMA / _NW / _RING / _SHORT / _FOLD / _XCD: A/B measurements and
  * the variant tests) are read from the environment once; a host that changes them afterwards calls this to have them read again. */
 int devqa_attention_reload_env(void);
 

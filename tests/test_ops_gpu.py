@@ -167,7 +167,7 @@ def _attention_case(name, g, rnd):
             causal, scale = 1, dh ** -0.5
         elif name in ("opt_pack_32", "llama_pack_32", "dh64_pack_32"):
             # the bench's decoder pack: 32-row image prefixes, texts of 1..32 rows behind them (<= 64 keys: one chunk) or alone, one text behind a
-            # LONG prefix (3 chunks) -- the wave-per-item pack kernel (opt-in) is run on it below
+            # LONG prefix (3 chunks) -- one-chunk prefix packs that every tiled form (forced below) must get right
             H, dh = {"opt_pack_32": (32, 80), "llama_pack_32": (8, 128), "dh64_pack_32": (12, 64)}[name]
             lens = [32, 5, 17, 31, 32, 25, 1, 16, 32, 9, 150, 20]
             pre = [None, 0, 0, 0, None, 4, 4, 4, None, None, None, 10]
@@ -235,10 +235,10 @@ def test_attention(L, name):
     # above, not the same bits; DEVQA_ATTENTION_FOLD=0 gives the unfolded form)
     import os
     outs = {}
-    base_env = {"DEVQA_ATTENTION_FOLD": "0", "DEVQA_ATTENTION_PACK": "0"}
+    base_env = {"DEVQA_ATTENTION_FOLD": "0"}
     for var in ({}, {"DEVQA_ATTENTION_DMA": "0"}, {"DEVQA_ATTENTION_DMA": "1", "DEVQA_ATTENTION_NW": "4"},
                 {"DEVQA_ATTENTION_DMA": "1", "DEVQA_ATTENTION_NW": "8"}, {"DEVQA_ATTENTION_DMA": "1", "DEVQA_ATTENTION_NW": "9"},
-                {"DEVQA_ATTENTION_NBUF": "3"}, {"DEVQA_ATTENTION_RING": "0"}, {"DEVQA_ATTENTION_SHORT": "0"}, {"DEVQA_ATTENTION_SHORT": "1"}):
+                {"DEVQA_ATTENTION_RING": "0"}, {"DEVQA_ATTENTION_SHORT": "0"}, {"DEVQA_ATTENTION_SHORT": "1"}):
         var = dict(base_env, **var)
         os.environ.update(var)
         try:
@@ -250,7 +250,7 @@ def test_attention(L, name):
         outs[tuple(sorted(var.items()))] = o.cpu()[keep]
     vals = list(outs.values())
     assert all(torch.equal(vals[0], x) for x in vals[1:])
-    for var in ({"DEVQA_ATTENTION_PACK": "1"}, {"DEVQA_ATTENTION_NBUF": "3"}, {"DEVQA_ATTENTION_NW": "8"}, {"DEVQA_ATTENTION_NW": "9"}):   # pack kernel up to 64 queries; ring forms with the fold
+    for var in ({"DEVQA_ATTENTION_NW": "8"}, {"DEVQA_ATTENTION_NW": "9"}):   # ring forms with the fold
         os.environ.update(var)
         try:
             o = L.attention(views[0], views[1], views[2], d, len(desc), max(x[1] for x in desc), H, dh, scale, causal)
@@ -258,29 +258,14 @@ def test_attention(L, name):
             for k_ in var:
                 del os.environ[k_]
         np.testing.assert_allclose(o.float().cpu()[keep].numpy(), ref[keep].numpy(), atol=2e-2, rtol=2e-2, err_msg=str(var))
-    if name == "vit":   # the opt-in K/V-resident kernel (self_full promise; enough (sequence, head) pairs to be selected: 8 x 16)
+    if name == "vit":   # the self_full promise (accepted, no effect on the kernel choice) on 8 images x 16 heads: the default kernel
         qkv8 = bf(torch.randn(8 * n, 3 * H * dh, generator=g))
         d8 = [(i * n, n, 0, 0, i * n, n) for i in range(8)]
         ref8 = _ref_attention(qkv8[:, :H * dh], qkv8[:, H * dh:2 * H * dh], qkv8[:, 2 * H * dh:], d8, H, dh, scale, 0)
         dq8 = dev(qkv8).to(torch.bfloat16)
         dd8 = torch.tensor(d8, dtype=torch.int32, device="cuda")
-        import os
-        os.environ["DEVQA_ATTENTION_RESIDENT"] = "1"
-        try:
-            o8 = L.attention(dq8[:, :H * dh], dq8[:, H * dh:2 * H * dh], dq8[:, 2 * H * dh:], dd8, 8, n, H, dh, scale, 0, self_full=True)
-        finally:
-            del os.environ["DEVQA_ATTENTION_RESIDENT"]
+        o8 = L.attention(dq8[:, :H * dh], dq8[:, H * dh:2 * H * dh], dq8[:, 2 * H * dh:], dd8, 8, n, H, dh, scale, 0, self_full=True)
         np.testing.assert_allclose(o8.float().cpu().numpy(), ref8.numpy(), atol=2e-2, rtol=2e-2)
-        o8c = L.attention(dq8[:, :H * dh], dq8[:, H * dh:2 * H * dh], dq8[:, 2 * H * dh:], dd8, 8, n, H, dh, scale, 0)
-        np.testing.assert_allclose(o8.float().cpu().numpy(), o8c.float().cpu().numpy(), atol=1e-2, rtol=1e-2)
-    if name == "vit":   # the experimental 128-query-tile instantiation (two query blocks per wave) on the same inputs
-        import os
-        os.environ["DEVQA_ATTENTION_QB"] = "2"
-        try:
-            out2 = L.attention(views[0], views[1], views[2], d, len(desc), max(x[1] for x in desc), H, dh, scale, causal)
-        finally:
-            del os.environ["DEVQA_ATTENTION_QB"]
-        np.testing.assert_allclose(out2.float().cpu().numpy(), ref.numpy(), atol=2e-2, rtol=2e-2)
 
 
 @pytest.mark.parametrize("name", ["vit", "qformer_cross", "opt_causal", "opt_prefix", "opt_pack_short", "llama_pack_short", "tiny_heads",
@@ -602,7 +587,7 @@ def test_column_compaction(L):
 
 
 def test_attention_is_deterministic_and_variants_agree(L):
-    """Multi-chunk causal sequences (> 64 keys: the K/V refill path) several times over, and the opt-in instantiations: bit-identical.
+    """Multi-chunk causal sequences (> 64 keys: the K/V refill path) several times over, and every forced staging: bit-identical.
     Guards the software-managed MFMA -> VALU read hazard of the inline-asm max chain (csrc/attention_mfma.hip, am_max16): without its
     wait states the running max was read stale now and then -- results within tolerance but different from run to run.
     The non-causal case takes the ring kernel by default (9-wave tiles; the last key of 65 / 129 / 257 is processed from LDS after the chunk loop
@@ -637,12 +622,6 @@ def test_attention_is_deterministic_and_variants_agree(L):
             else:
                 err = (base.float() - folded.float()).abs().max().item()
                 assert err < 4e-2, err                     # (the folded key's fp32 score comes from a VALU fma chain: an output may move by a bf16 ulp)
-            for var in ("DEVQA_ATTENTION_DBUF", "DEVQA_ATTENTION_QB"):
-                os.environ[var] = "1" if var.endswith("DBUF") else "2"
-                try:
-                    assert torch.equal(run(), base), var
-                finally:
-                    del os.environ[var]
             for dma, nw in (("0", "4"), ("1", "4"), ("1", "8"), ("1", "9")):      # both stagings, the tile sizes of the LDS-DMA / ring kernels
                 os.environ["DEVQA_ATTENTION_DMA"], os.environ["DEVQA_ATTENTION_NW"] = dma, nw
                 try:

@@ -23,7 +23,7 @@ for (lens, name) in (([104, 30, 70, 129, 64, 65], "causal-own"),):
             qf = q[s:s + n].float().view(n, H, dh).transpose(0, 1); kf = k[s:s + n].float().view(n, H, dh).transpose(0, 1); vf = v[s:s + n].float().view(n, H, dh).transpose(0, 1)
             sc = qf @ kf.transpose(-1, -2) * dh ** -0.5 + torch.full((n, n), float("-inf"), device="cuda").triu(1)
             ref[s:s + n] = (torch.softmax(sc, -1) @ vf).transpose(0, 1).reshape(n, d)
-        for env in ({}, {"DEVQA_ATTENTION_DBUF": "1"}, {"DEVQA_ATTENTION_QB": "2"}):
+        for env in ({},):
             os.environ.update(env)
             outs = []
             for it in range(6):

@@ -64,7 +64,7 @@ def main(cycles=16):
         us = t_us(fn)
         print("%-26s %8.1f us   (%.0f TFLOP/s on the whole pack's %.1f GFLOP)" % (name, us, flops / us / 1e6, flops / 1e9))
     ref = out1.clone()
-    for var in ({"DEVQA_ATTENTION_NW": "4"}, {"DEVQA_ATTENTION_DMA": "0"}, {"DEVQA_ATTENTION_RING": "2"}, {"DEVQA_ATTENTION_RING": "2", "DEVQA_ATTENTION_NBUF": "3"}):
+    for var in ({"DEVQA_ATTENTION_NW": "4"}, {"DEVQA_ATTENTION_DMA": "0"}, {"DEVQA_ATTENTION_RING": "2"}):
         os.environ.update(var)
         out1.zero_()
         one()

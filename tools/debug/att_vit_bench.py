@@ -38,8 +38,6 @@ def main():
         variants = (("ring, 9 waves", {"DEVQA_ATTENTION_NW": "9"}), ("ring, 8 waves", {"DEVQA_ATTENTION_NW": "8"}),
                     ("ring, 9 waves, no fold", {"DEVQA_ATTENTION_NW": "9", "DEVQA_ATTENTION_FOLD": "0"}),
                     ("ring, 8 waves, no fold", {"DEVQA_ATTENTION_NW": "8", "DEVQA_ATTENTION_FOLD": "0"}),
-                    ("ring, 9 waves, 3 images", {"DEVQA_ATTENTION_NW": "9", "DEVQA_ATTENTION_NBUF": "3"}),
-                    ("ring, 8 waves, 3 images", {"DEVQA_ATTENTION_NW": "8", "DEVQA_ATTENTION_NBUF": "3"}),
                     ("two-image DMA, 8 waves", {"DEVQA_ATTENTION_RING": "0"}), ("two-image DMA, 4 waves", {"DEVQA_ATTENTION_RING": "0", "DEVQA_ATTENTION_NW": "4"}),
                     ("register-staged", {"DEVQA_ATTENTION_DMA": "0"}))
         best, outs = {}, {}
