@@ -5,7 +5,11 @@
 // lane = channel for the accumulation phase.
 //
 // Supports the own-key part of the packed descriptor only (kp_len == 0: every sequence attends to its own rows,
-// causal or full) -- what the edit path packs.  Two kernels:
+// causal or full) -- what the edit path packs.  The visible-prefix fields of a descriptor (kp_start, kp_len) are NOT
+// read and nothing rejects a descriptor that sets them: for kp_len != 0 the results are the gradients of attention
+// over the own keys alone -- the prefix keys get no gradient from those queries, dq has no term from them (pinned by
+// tests/test_attention_bwd_gpu.py::test_visible_prefix_is_ignored; no caller packs a prefix for a backward pass).
+// Two kernels:
 //   dq   : per query row i: L_i = logsumexp_j(s_ij), D_i = dO_i . O_i, dq_i = scale * sum_j P_ij (dP_ij - D_i) k_j
 //   dkdv : per key row j  : dv_j = sum_i P_ij dO_i,  dk_j = scale * sum_i P_ij (dP_ij - D_i) q_i
 // with s_ij = scale * q_i . k_j, P = softmax(s), dP_ij = dO_i . v_j.  stats[(row, head)] = (L_i, D_i) is written by dq
@@ -216,8 +220,9 @@ template <typename T>
 static int attention_bwd_impl(const T* q, int64_t ldq, const T* k, int64_t ldk, const T* v, int64_t ldv, const T* o, int64_t ldo,
                               const T* dO, int64_t lddo, T* dq, int64_t lddq, T* dk, int64_t lddk, T* dv, int64_t lddv, float* stats,
                               const int32_t* seq_desc, int n_seq, int max_len, int H, int dh, float scale, int causal, void* stream) {
-    DEVQA_CHECK_ARG(q && k && v && o && dO && dq && dk && dv && stats && seq_desc, "attention_bwd: null pointer");
+    // sizes first: with dh == 0 the caller's tensors are empty and may well have null pointers -- still a shape error
     DEVQA_CHECK_SHAPE(n_seq > 0 && max_len > 0 && H > 0 && dh > 0 && dh <= AB_DH, "attention_bwd: bad sizes (dh <= 128)");
+    DEVQA_CHECK_ARG(q && k && v && o && dO && dq && dk && dv && stats && seq_desc, "attention_bwd: null pointer");
     const int blocks = (max_len + AB_RB - 1) / AB_RB;
     const long grid = (long)n_seq * H * blocks;
     DEVQA_CHECK_SHAPE(grid < 2147483647L, "attention_bwd: grid too large");

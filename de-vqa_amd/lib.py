@@ -739,7 +739,10 @@ def cosine_topk(corpus, queries, k, normalize_corpus=True, normalize_queries=Tru
 
 
 def attention_bwd(q, k, v, o, d_out, seq_desc, n_seq, max_len, H, dh, scale, causal):
-    """Gradients (dq, dk, dv) of `attention` for descriptors without a visible prefix (kp_len == 0)."""
+    """Gradients (dq, dk, dv) of `attention` for descriptors without a visible prefix (kp_len == 0).
+    Nothing enforces that: the kernels do not read kp_start / kp_len, so for a descriptor with kp_len != 0 the results are silently the
+    gradients of attention over the OWN keys alone (the prefix keys receive no gradient from those queries and dq lacks their term).
+    tests/test_attention_bwd_gpu.py::test_visible_prefix_is_ignored pins this; every caller packs own-key descriptors for a backward."""
     for t in (q, k, v, o, d_out):
         assert t.dtype == q.dtype and t.is_cuda and t.dim() == 2 and t.stride(1) == 1
     assert q.dtype in (torch.bfloat16, torch.float32)

@@ -7,6 +7,7 @@ import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 _OPS = "tests/test_ops_gpu.py::"
+_ABWD = "tests/test_attention_bwd_gpu.py::"
 _LLAMA = "tests/test_llama_ops_gpu.py::"
 _MEND = "tests/test_mend_train_ops_gpu.py::"
 _TP = "tests/test_tp_neuron_ops_gpu.py::"
@@ -35,8 +36,8 @@ COVERED_BY = {
     "devqa_attention": _OPS + "test_attention",
     "devqa_attention_f32": _OPS + "test_attention_f32",
     "devqa_attention_reload_env": _OPS + "test_attention",
-    "devqa_attention_bwd": _OPS + "test_attention_bwd_vs_autograd",
-    "devqa_attention_bwd_f32": _OPS + "test_attention_bwd_vs_autograd",
+    "devqa_attention_bwd": _ABWD + "test_head_dims",
+    "devqa_attention_bwd_f32": _ABWD + "test_head_dims",
     "devqa_im2col_patches": _OPS + "test_patch_embed_and_assemble",
     "devqa_im2col_patches_f32": _OPS + "test_patch_embed_and_assemble",
     "devqa_vit_assemble": _OPS + "test_patch_embed_and_assemble",

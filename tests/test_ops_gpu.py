@@ -1,7 +1,8 @@
 """Op-level parity of C-ABI entry points against plain PyTorch on the CPU, on the same (bf16-rounded) inputs: the GEMMs, LayerNorm, both
 attention forwards and the backward, the vision / embedding / vocabulary row ops, the FT_VL step, retrieval top-k and column compaction.
 The LLaMA row ops are in tests/test_llama_ops_gpu.py, the MEND / LTE training row ops in tests/test_mend_train_ops_gpu.py, the T-Patcher
-neuron ops in tests/test_tp_neuron_ops_gpu.py; tests/test_op_coverage_cpu.py names the test that holds each exported symbol.
+neuron ops in tests/test_tp_neuron_ops_gpu.py, the attention backward at the shapes training runs (head dims to 128, several chunks, strides,
+padded packs) in tests/test_attention_bwd_gpu.py; tests/test_op_coverage_cpu.py names the test that holds each exported symbol.
 Integer outputs (argmax, top-k ids) must match exactly; floating point tolerances are written per test."""
 import numpy as np
 import pytest
